@@ -16,13 +16,21 @@ torchrun environment starts the N ranks itself (a torch.distributed.run child
 process, launched before anything touches the GPU) and exits with the worst
 rank's status; under torchrun (WORLD_SIZE set) it is one rank.
 
-Besides the headline, rank 0 reports (after the timed steps, outside the
-driver's clock contract): BASELINE config 2 (480x640, B=32), the config-3
-hole-fill, the fused first-stage warps, the config-5 bf16 warp, and the CPU
-baselines of BASELINE.md §3 (the C loop, the torch-CPU scatter-min warp and
-the torch-CPU geometry flow) on this box's host cores.
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, write the outputs if --dump-outputs is given, print the line.  With
+--full, rank 0 also reports (after the timed steps, outside the driver's
+clock contract): BASELINE config 2 (480x640, B=32), the config-3 hole-fill,
+the fused first-stage warps, the config-5 bf16 warp, and the CPU baselines of
+BASELINE.md §3 (the C loop, the torch-CPU scatter-min warp and the torch-CPU
+geometry flow) on the host's cores; each has a --no-... switch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+--dump-outputs DIR writes what the last timed step returned (rank 0's shard:
+output, valid, collision) as DIR/<name>.npy, float32: whole arrays when they
+fit DUMP_BYTES together, else a fixed seeded sample of each (dump_outputs).
+The inputs are seeded, so two builds can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-config2] ...]
 """
 from __future__ import annotations
 
@@ -54,6 +62,12 @@ def parse(argv=None):
     ap.add_argument("--height", type=int, default=768)
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--ego-fraction", type=float, default=0.5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the phases beside the headline: CPU baselines, "
+                         "config 2, fused warps, bf16 warp, hole-fill (each has a --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; a fixed seeded sample "
+                         "of each array when they exceed DUMP_BYTES together)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline wall budget (headline leg)")
     ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "0") or 0))
@@ -66,7 +80,10 @@ def parse(argv=None):
     ap.add_argument("--no-config2", action="store_true", help="skip the config-2 (480x640, B=32) phase")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective / timing skeleton only, on CPU with gloo (tests)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------- launcher
@@ -125,6 +142,32 @@ def timed_events(fn, steps, stream):
         b.record(stream)
     torch.cuda.synchronize()
     return sum(a.elapsed_time(b) for a, b in ev) / steps
+
+
+DUMP_BYTES = 56 * 1000 * 1000  # all dumped arrays together (the limit is 64 MB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, named):
+    """Write each (name, tensor) as dirname/name.npy in float32.  Arrays that
+    fit DUMP_BYTES together are written whole, in their own shape.  Otherwise
+    each array gives a 1-D sample of its flattened elements, its share of the
+    budget in proportion to its size, at sorted positions drawn from a
+    generator seeded by DUMP_SEED and the array's place in the list: the same
+    shapes give the same positions in every run and every build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() for _, t in named)
+    budget = DUMP_BYTES // 4
+    for i, (name, t) in enumerate(named):
+        if total <= budget:
+            a = t.detach().to(torch.float32).cpu().numpy()
+        else:
+            k = max(1, budget * t.numel() // total)
+            pos = np.sort(np.random.default_rng([DUMP_SEED, i]).integers(0, t.numel(), size=k, dtype=np.int64))
+            idx = torch.from_numpy(pos).to(t.device)
+            a = t.detach().reshape(-1)[idx].to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def sample_idx(B, n):
@@ -600,6 +643,9 @@ def main(argv=None):
     wall = time.perf_counter() - t0
     lib.ofd_fw_set_profile_events(None, None)
     lib.ofd_fw_set_profile_bin_event(None)
+    if args.dump_outputs and rank == 0:
+        progress(f"writing outputs to {args.dump_outputs}")
+        dump_outputs(args.dump_outputs, list(zip(("output", "valid", "collision"), out)))
     ev_ms = [s.elapsed_time(e) for s, e in zip(starts, ends)] if evmode >= 2 else [wall * 1e3 / args.steps]
     dev_ms = sum(ev_ms) / len(ev_ms)
     rv_ms = [rstarts[k].elapsed_time(rends[k]) for k in sampled] if evmode >= 1 else [dev_ms]
@@ -670,30 +716,30 @@ def main(argv=None):
 
     cpu = None
     threads = args.cpu_threads if args.cpu_threads > 0 else min(16, os.cpu_count() or 1)
-    cpu_on = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_on = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     progress(f"headline {wall / args.steps * 1e3:.4f} ms/step")
     if cpu_on:
         progress("cpu baseline")
         cpu = cpu_baseline(obj, flow, depth, args.cpu_seconds, threads)
 
     cfg2 = None
-    if rank == 0 and not args.no_config2:
+    if args.full and rank == 0 and not args.no_config2:
         progress("config 2")
         cfg2 = config2_phase(60, dev, stream, threads, args.cpu_seconds / 2 if cpu_on else 0)
 
     fused = fused_ego = None
-    if rank == 0 and not args.no_fused:
+    if args.full and rank == 0 and not args.no_fused:
         progress("fused warps")
         fused = fused_disparity_phase(B, H, W, 10, dev, stream)
         fused_ego = fused_ego_phase(B, H, W, 10, dev, stream)
 
     bf16 = None
-    if rank == 0 and not args.no_bf16:
+    if args.full and rank == 0 and not args.no_bf16:
         progress("bf16 warp")
         bf16 = bf16_warp_phase(64, 368, 560, 20, dev, stream)
 
     hole = None
-    if rank == 0 and not args.no_hole_fill:  # untimed by the driver's clock contract: after the K steps
+    if args.full and rank == 0 and not args.no_hole_fill:  # untimed by the driver's clock contract: after the K steps
         progress("hole-fill")
         rgb, res, hole = hole_fill_phase(out[0], out[1], out[2], args.hole_fill_steps, stream)
         if cpu_on:

@@ -12,7 +12,7 @@ for round in $(seq "$ROUNDS"); do
       base:*) envv="${v#base:}" ;;
       *) lib="$PWD/opticalflowfromdepth_amd/_build/libofd_fw_$v.so" ;;
     esac
-    env "$envv" OFD_FW_LIB=$lib timeout -k 10 120 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-hole-fill \
+    env "$envv" OFD_FW_LIB=$lib timeout -k 10 120 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-hole-fill \
         --no-fused --no-config2 > /tmp/ab_bf16.json 2>/dev/null || exit 1
     python3 -c "import json; d=json.loads(open('/tmp/ab_bf16.json').read().strip().splitlines()[-1]); b=d['bf16_warp']; print('$v', b['ms_per_step'], b['f32_ms_per_step'], round(1 - b['ms_per_step'] / b['f32_ms_per_step'], 4), b['equals_f32_path'])"
   done
