@@ -38,6 +38,30 @@ size_t ofd_deflate_workspace_bytes(int64_t count, int64_t bytes_each);
 int ofd_deflate_batch(const void *in, int64_t count, int64_t bytes_each, void *out, uint64_t *sizes, uint32_t *crcs,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- match mode (opt-in): the same blocks with LZ77 matches at the element
+ * stride.  Every 64-byte span is parsed greedily: the longest run of bytes
+ * equal to the byte D before them, D in {1, elem_bytes, 2 * elem_bytes}, is
+ * coded as a match when it is 3 bytes or longer and stays inside the span.
+ * Same stream format, slots, sizes, CRCs and return codes as above; the
+ * streams are smaller wherever the data repeats at those distances. */
+
+/* Output slot bytes per array (a multiple of 256). */
+size_t ofd_deflate_lz_bound(int64_t bytes_each);
+
+/* Workspace bytes for ofd_deflate_lz_batch(count, bytes_each). */
+size_t ofd_deflate_lz_workspace_bytes(int64_t count, int64_t bytes_each);
+
+/* As ofd_deflate_batch, slots at out + i * ofd_deflate_lz_bound(bytes_each).
+ * elem_bytes is the size of the arrays' elements: 1, 2, 4 or 8 (anything else:
+ * OFD_FW_EINVAL); bytes_each need not be a multiple of it. */
+int ofd_deflate_lz_batch(const void *in, int64_t count, int64_t bytes_each, int elem_bytes, void *out, uint64_t *sizes,
+                         uint32_t *crcs, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Measurement knob: which candidate distances besides elem_bytes the parse
+ * tries.  Bit 0: distance 1, bit 1: distance 2 * elem_bytes; default 3 (both).
+ * Process-wide; not for use while a call is being issued on another thread. */
+int ofd_deflate_lz_set_candidates(int mask);
+
 #ifdef __cplusplus
 }
 #endif

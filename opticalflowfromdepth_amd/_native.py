@@ -69,6 +69,10 @@ SIGNATURES = {
     "ofd_deflate_bound": ([_I64], _SZ),
     "ofd_deflate_workspace_bytes": ([_I64, _I64], _SZ),
     "ofd_deflate_batch": ([_P, _I64, _I64, _P, _P, _P, _P, _SZ, _P], ctypes.c_int),
+    "ofd_deflate_lz_bound": ([_I64], _SZ),
+    "ofd_deflate_lz_workspace_bytes": ([_I64, _I64], _SZ),
+    "ofd_deflate_lz_batch": ([_P, _I64, _I64, ctypes.c_int, _P, _P, _P, _P, _SZ, _P], ctypes.c_int),
+    "ofd_deflate_lz_set_candidates": ([ctypes.c_int], ctypes.c_int),
 }
 
 

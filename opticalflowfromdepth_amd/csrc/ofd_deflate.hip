@@ -32,11 +32,21 @@
 //          atomics; the chunk holding a segment's start writes the header,
 //          the one holding its end the end-of-block code and FF FF.
 //
+// ofd_deflate_lz_batch (opt-in, second half of this file) is the same
+// structure with LZ77 matches: every thread parses its 64-byte span greedily
+// for runs equal to the bytes 1, E or 2E back (E = the element size), HIST
+// counts 286 literal / length and 30 distance symbols plus the matches' extra
+// bits, CODE builds two trees and sends HLIT / HDIST, ENCODE runs the same
+// parse again and emits the tokens.  ofd_deflate_batch and its bytes do not
+// change.
+//
 // Plain HIP for gfx950.
 
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+
+#include <utility>
 
 #include "ofd_deflate.h"
 #include "ofd_fw.h"
@@ -104,6 +114,7 @@ struct DWs {
     uint32_t *sbytes;  // [segs] segment bytes (header .. FF FF)
     uint32_t *scrc;    // [segs]
     uint64_t *soff;    // [segs] byte offset of the segment in its array's slot
+    uint32_t *cxb;     // [chunks] extra bits of the chunk's matches (match mode only)
 };
 
 size_t ws_bytes(int64_t count, int64_t each) {
@@ -127,6 +138,7 @@ DWs carve(void *ws, int64_t count, const Geo &g) {
     w.sbytes = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
     w.scrc = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
     w.soff = reinterpret_cast<uint64_t *>(p);
+    w.cxb = nullptr;
     return w;
 }
 
@@ -525,6 +537,444 @@ __global__ __launch_bounds__(kThr) void dfl_encode_kernel(const uint8_t *__restr
     }
 }
 
+// ================================================================ match mode
+// ofd_deflate_lz_batch: the same segments, chunks, spans and kernels, with
+// LZ77 matches at the element stride.  Every thread parses its own 64-byte
+// span greedily: at byte p it takes the longest run b[p+i] == b[p+i-D] over
+// the candidate distances D in {1, E, 2E} (E = the caller's element size; the
+// smaller D on ties) that stays inside the span, and codes it as a match when
+// it is kMinMatch bytes or more, else b[p] as a literal.  A match may read the
+// 2E <= 16 bytes before the span (they are input too), never bytes before its
+// own array.  The parse is a pure function of the span and those 16 bytes
+// (parse_span), so HIST and ENCODE both run it and no token is ever stored.
+constexpr int kLSym = 286;    // literals, end of block, 29 length symbols
+constexpr int kDSym = 30;     // distance symbols
+constexpr int kDOff = kLSym;  // the distance symbols follow in the joint tables ...
+constexpr int kAll = 320;     // ... of 316 entries, padded
+constexpr int kMinMatch = 3;
+constexpr int kCandDefault = 3;  // bit 0: distance 1, bit 1: distance 2E (E itself always)
+static_assert(kPerThr == 64, "a span's equality masks are 64-bit");
+// BFINAL BTYPE HLIT HDIST HCLEN, 19 code-length-code lengths, 316 lengths of <= 7 bits
+static_assert(14 + 19 * 3 + (kLSym + kDSym) * 7 <= kHdrWords * 32, "the block header must fit kHdrWords");
+
+int g_lz_cand = kCandDefault;
+
+size_t lz_ws_bytes(int64_t count, int64_t each) {
+    const int64_t cpa = (each + kChunk - 1) / kChunk, spa = (each + kSeg - 1) / kSeg;
+    const size_t nc = size_t(count * cpa), ns = size_t(count * spa);
+    return align256(nc * 2 * kAll) + 2 * align256(nc * 4) + align256(nc * 8) + 2 * align256(ns * 4 * kAll) +
+           align256(ns * 4 * kHdrWords) + 3 * align256(ns * 4) + align256(ns * 8);
+}
+
+DWs lz_carve(void *ws, int64_t count, const Geo &g) {
+    const size_t nc = size_t(count) * g.cpa, ns = size_t(count) * g.spa;
+    char *p = static_cast<char *>(ws);
+    DWs w;
+    w.chist = reinterpret_cast<uint16_t *>(p), p += align256(nc * 2 * kAll);  // [chunks][kAll]
+    w.ccrc = reinterpret_cast<uint32_t *>(p), p += align256(nc * 4);
+    w.cxb = reinterpret_cast<uint32_t *>(p), p += align256(nc * 4);
+    w.cbit = reinterpret_cast<uint64_t *>(p), p += align256(nc * 8);
+    w.shist = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kAll);  // [segs][kAll]  (zeroed per call)
+    w.scode = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kAll);  // [segs][kAll]
+    w.shdr = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kHdrWords);
+    w.shbits = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
+    w.sbytes = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
+    w.scrc = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
+    w.soff = reinterpret_cast<uint64_t *>(p);
+    return w;
+}
+
+// The 16 bytes before a span (zeros when there are none to read)
+__device__ __forceinline__ void load_hist16(const uint8_t *p, bool have, uint32_t hs[4]) {
+    hs[0] = hs[1] = hs[2] = hs[3] = 0u;
+    if (!have) return;
+    const uint8_t *h = p - 16;
+    if ((reinterpret_cast<uintptr_t>(h) & 15u) == 0) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(h);
+        hs[0] = v.x, hs[1] = v.y, hs[2] = v.z, hs[3] = v.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) hs[q] |= uint32_t(h[4 * q + r]) << (8 * r);
+    }
+}
+
+// ext = 16 history bytes then the span's 64, as 20 little-endian words.
+// Bit i of the result: span byte i equals the byte D before it.
+template <int D, int q>
+__device__ __forceinline__ uint64_t eq_nibble(const uint32_t ext[20]) {  // the mask's bits 4q .. 4q + 3
+    uint32_t prev;
+    if constexpr (D % 4 == 0)
+        prev = ext[4 + q - D / 4];
+    else
+        prev = uint32_t(((uint64_t(ext[4 + q]) << 32) | ext[3 + q]) >> (8 * (4 - D)));
+    const uint32_t x = ext[4 + q] ^ prev;
+    uint32_t t = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);  // 0x80 in every zero byte of x
+    t >>= 7;
+    return uint64_t((t | (t >> 7) | (t >> 14) | (t >> 21)) & 0xFu) << (4 * q);
+}
+
+template <int D, int... Q>
+__device__ __forceinline__ uint64_t eq_mask_seq(const uint32_t ext[20], std::integer_sequence<int, Q...>) {
+    return (eq_nibble<D, Q>(ext) | ...);
+}
+
+template <int D>
+__device__ __forceinline__ uint64_t eq_mask(const uint32_t ext[20]) {
+    static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16, "distance");
+    return eq_mask_seq<D>(ext, std::make_integer_sequence<int, 16>{});
+}
+
+// RFC 1951 3.2.5 for the distances in use (powers of two up to 16)
+__device__ __forceinline__ constexpr int dist_sym(int D) { return D == 1 ? 0 : D == 2 ? 1 : D == 4 ? 3 : D == 8 ? 5 : 7; }
+__device__ __forceinline__ constexpr int dist_xbits(int D) { return D == 8 ? 1 : D == 16 ? 2 : 0; }
+__device__ __forceinline__ constexpr uint32_t dist_xval(int D) { return D == 8 ? 1u : D == 16 ? 3u : 0u; }
+
+// length 3..257 -> symbol, extra bit count and value (258 is never emitted: a span has 64 bytes)
+__device__ __forceinline__ void len_sym(int len, int &sym, int &xb, uint32_t &xv) {
+    const int x = len - 3;
+    if (x < 8) {
+        sym = 257 + x, xb = 0, xv = 0u;
+    } else {
+        const int k = 29 - __clz(x);  // 8..15: 1 extra bit, 16..31: 2, 32..63: 3, ...
+        sym = 257 + 4 * (k + 1) + ((x >> k) & 3), xb = k, xv = uint32_t(x) & ((1u << k) - 1u);
+    }
+}
+
+// The greedy parse of one span: tok(e, is_match, length, D) for every token,
+// in order; e is the token's first byte as a std::integral_constant, so that
+// every index into the span's registers is a constant.  n = the span's bytes,
+// first = the span starts its array (no history to match).
+template <int E>
+struct SpanMasks {
+    uint64_t m1, me, m2;  // distance 1 (E > 1 only), E, 2E
+};
+
+template <int E>
+__device__ __forceinline__ SpanMasks<E> span_masks(const uint32_t ext[20], int n, bool first, int cand) {
+    const uint64_t live = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+    SpanMasks<E> m{0, 0, 0};
+    if (E > 1 && (cand & 1)) m.m1 = eq_mask<1>(ext) & live & (first ? ~0ull << 1 : ~0ull);
+    m.me = eq_mask<E>(ext) & live & (first ? ~0ull << E : ~0ull);
+    if (cand & 2) m.m2 = eq_mask<2 * E>(ext) & live & (first ? ~0ull << (2 * E) : ~0ull);
+    return m;
+}
+
+template <int e, int E, class F>
+__device__ __forceinline__ void parse_step(const SpanMasks<E> &m, int n, int &next, F &tok) {
+    if (e == next && e < n) {
+        auto run = [](uint64_t x) -> int {
+            const uint64_t y = ~(x >> e);
+            return y ? __builtin_ctzll(y) : 64;
+        };
+        int best = E > 1 ? run(m.m1) : 0, D = 1;
+        const int re = run(m.me), r2 = run(m.m2);
+        if (re > best) best = re, D = E;
+        if (r2 > best) best = r2, D = 2 * E;
+        const bool match = best >= kMinMatch;
+        tok(std::integral_constant<int, e>{}, match, best, D);
+        next = e + (match ? best : 1);
+    }
+}
+
+template <int E, class F, int... I>
+__device__ __forceinline__ void parse_steps(const SpanMasks<E> &m, int n, F &tok, std::integer_sequence<int, I...>) {
+    int next = 0;
+    (parse_step<I, E>(m, n, next, tok), ...);
+}
+
+template <int E, class F>
+__device__ __forceinline__ void parse_span(const SpanMasks<E> &m, int n, F &&tok) {
+    parse_steps<E>(m, n, tok, std::make_integer_sequence<int, kPerThr>{});
+}
+
+// byte e of the span in ext (e a constant)
+template <int e>
+__device__ __forceinline__ uint32_t span_byte(const uint32_t ext[20]) {
+    return (ext[4 + (e >> 2)] >> (8 * (e & 3))) & 0xFFu;
+}
+
+template <int E>
+__global__ __launch_bounds__(kThr) void dfl_lz_hist_kernel(const uint8_t *__restrict__ in, Geo g, DWs w, int cand) {
+    __shared__ uint32_t T[256];
+    __shared__ uint32_t H[kAll];
+    __shared__ uint32_t C[kThr];
+    __shared__ uint32_t X;
+    const int c = blockIdx.x, a = c / g.cpa, k = c - a * g.cpa;
+    const int64_t beg = int64_t(k) * kChunk, len = min(kChunk, g.each - beg);
+    const uint8_t *src = in + int64_t(a) * g.each + beg;
+    make_crc_table(T);
+    for (int i = threadIdx.x; i < kAll; i += kThr) H[i] = 0u;
+    if (threadIdx.x == 0) X = 0u;
+    __syncthreads();
+    const int t0 = threadIdx.x * kPerThr;
+    const int n = int(min<int64_t>(kPerThr, max<int64_t>(len - t0, 0)));
+    uint32_t ext[20];
+    load_hist16(src + t0, n > 0 && beg + t0 > 0, ext);
+    load64(src, t0, n, ext + 4);
+    uint32_t crc = 0xFFFFFFFFu;
+#pragma unroll
+    for (int e = 0; e < kPerThr; ++e)
+        if (e < n) crc = T[(crc ^ (ext[4 + (e >> 2)] >> (8 * (e & 3)))) & 0xFFu] ^ (crc >> 8);
+    crc = ~crc;
+    uint32_t zeros = 0, xbits = 0;
+    const SpanMasks<E> sm = span_masks<E>(ext, n, beg + t0 == 0, cand);
+    parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) {
+        if (!match) {
+            const uint32_t b = span_byte<decltype(e)::value>(ext);
+            if (b == 0u)
+                ++zeros;
+            else
+                atomicAdd(&H[b], 1u);
+        } else {
+            int sym, xb;
+            uint32_t xv;
+            len_sym(mlen, sym, xb, xv);
+            atomicAdd(&H[sym], 1u);
+            atomicAdd(&H[kDOff + dist_sym(D)], 1u);
+            xbits += uint32_t(xb + dist_xbits(D));
+        }
+    });
+    // zero literals dominate what is left: one wave sum, as in the literal HIST
+    for (int d = 32; d > 0; d >>= 1) {
+        zeros += __shfl_xor(zeros, d);
+        xbits += __shfl_xor(xbits, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (zeros) atomicAdd(&H[0], zeros);
+        if (xbits) atomicAdd(&X, xbits);
+    }
+    C[threadIdx.x] = crc;
+    __syncthreads();
+    for (int s = 1; s < kThr; s <<= 1) {
+        if ((threadIdx.x & (2 * s - 1)) == 0 && threadIdx.x + s < kThr) {
+            const int64_t lb = min<int64_t>(int64_t(s) * kPerThr, max<int64_t>(len - int64_t(threadIdx.x + s) * kPerThr, 0));
+            if (lb > 0) C[threadIdx.x] = crc_combine(C[threadIdx.x], C[threadIdx.x + s], uint64_t(lb));
+        }
+        __syncthreads();
+    }
+    const int seg = a * g.spa + int(beg / kSeg);
+    for (int i = threadIdx.x; i < kAll; i += kThr) {
+        const uint32_t h = H[i];
+        w.chist[int64_t(c) * kAll + i] = uint16_t(h);
+        if (h) atomicAdd(&w.shist[int64_t(seg) * kAll + i], h);
+    }
+    if (threadIdx.x == 0) {
+        w.ccrc[c] = len > 0 ? C[0] : 0u;
+        w.cxb[c] = X;
+    }
+}
+
+// Two trees per segment: literal / length (<= 286 symbols) and distance (<= 30).
+// zlib's inflater accepts exactly these distance codes: no match in the
+// segment -> one distance length 0; one distance symbol -> that symbol with
+// length 1 (incomplete, allowed); two or more -> a complete (Huffman) code.
+__global__ __launch_bounds__(kThr) void dfl_lz_code_kernel(Geo g, DWs w) {
+    __shared__ HuffLds L;
+    __shared__ uint32_t f[512];
+    __shared__ uint32_t code[kAll];  // [0, 286) literal / length, [286, 316) distance
+    __shared__ uint32_t hdr[kHdrWords];
+    __shared__ uint32_t clf[19];
+    __shared__ uint32_t clcode[19];
+    __shared__ uint64_t cb[kChunksPerSeg];
+    __shared__ int s_hlit, s_hdist, s_nd;
+    const int s = blockIdx.x, a = s / g.spa, k = s - a * g.spa;
+    const int64_t sbeg = int64_t(k) * kSeg, slen = min(kSeg, g.each - sbeg);
+    const int c0 = a * g.cpa + int(sbeg / kChunk), nch = int((slen + kChunk - 1) / kChunk);
+    const uint32_t *sh = w.shist + int64_t(s) * kAll;
+    for (int i = threadIdx.x; i < 512; i += kThr) f[i] = i == 256 ? 1u : (i < kLSym ? sh[i] : 0u);
+    for (int i = threadIdx.x; i < kHdrWords; i += kThr) hdr[i] = 0u;
+    for (int i = threadIdx.x; i < kAll; i += kThr) code[i] = 0u;
+    if (threadIdx.x == 0) {
+        int hlit = 257, hdist = 1, nd = 0;
+        for (int i = 257; i < kLSym; ++i)
+            if (sh[i]) hlit = i + 1;
+        for (int i = 0; i < kDSym; ++i)
+            if (sh[kDOff + i]) hdist = i + 1, ++nd;
+        s_hlit = hlit, s_hdist = hdist, s_nd = nd;
+    }
+    __syncthreads();
+    huff_lengths(f, kLSym, kMaxLen, L);
+    if (threadIdx.x == 0) canonical(L.len, kLSym, code);
+    __syncthreads();
+    if (s_nd > 0) {  // the same in every thread
+        for (int i = threadIdx.x; i < 512; i += kThr) f[i] = i < kDSym ? sh[kDOff + i] : 0u;
+        __syncthreads();
+        huff_lengths(f, kDSym, kMaxLen, L);
+        if (threadIdx.x == 0) canonical(L.len, kDSym, code + kDOff);
+        __syncthreads();
+    }
+    const int hlit = s_hlit, hdist = s_hdist;
+    // code-length code over the hlit + hdist lengths sent
+    if (threadIdx.x < 19) clf[threadIdx.x] = 0u;
+    __syncthreads();
+    for (int i = threadIdx.x; i < hlit; i += kThr) atomicAdd(&clf[code[i] >> 24], 1u);
+    for (int i = threadIdx.x; i < hdist; i += kThr) atomicAdd(&clf[code[kDOff + i] >> 24], 1u);
+    __syncthreads();
+    huff_lengths(clf, 19, 7, L);
+    if (threadIdx.x == 0) {
+        canonical(L.len, 19, clcode);
+        static const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+        int hclen = 19;
+        while (hclen > 4 && L.len[order[hclen - 1]] == 0) --hclen;
+        uint32_t pos = 0;
+        put_bits(hdr, pos, 0u, 1);  // BFINAL 0
+        put_bits(hdr, pos, 2u, 2);  // BTYPE 2 (dynamic)
+        put_bits(hdr, pos, uint32_t(hlit - 257), 5);
+        put_bits(hdr, pos, uint32_t(hdist - 1), 5);
+        put_bits(hdr, pos, uint32_t(hclen - 4), 4);
+        for (int i = 0; i < hclen; ++i) put_bits(hdr, pos, L.len[order[i]], 3);
+        for (int i = 0; i < hlit + hdist; ++i) {
+            const uint32_t l = code[i < hlit ? i : kDOff + i - hlit] >> 24;
+            put_bits(hdr, pos, clcode[l] & 0xFFFFFFu, int(clcode[l] >> 24));
+        }
+        w.shbits[s] = pos;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kHdrWords; i += kThr) w.shdr[int64_t(s) * kHdrWords + i] = hdr[i];
+    for (int i = threadIdx.x; i < kAll; i += kThr) w.scode[int64_t(s) * kAll + i] = code[i];
+    // chunk bit counts: its symbols' code lengths plus its matches' extra bits; one wave per chunk
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int q = wave; q < nch; q += kThr / 64) {
+        uint32_t bits = 0;
+        for (int i = lane; i < kAll; i += 64) bits += uint32_t(w.chist[int64_t(c0 + q) * kAll + i]) * (code[i] >> 24);
+        for (int d = 32; d > 0; d >>= 1) bits += __shfl_xor(bits, d);
+        if (lane == 0) cb[q] = uint64_t(bits) + w.cxb[c0 + q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t acc = w.shbits[s];
+        for (int q = 0; q < nch; ++q) {
+            w.cbit[c0 + q] = acc;
+            acc += cb[q];
+        }
+        acc += code[256] >> 24;                    // end of block
+        acc += 3;                                  // sync flush: an empty stored block's header ...
+        const uint64_t bytes = (acc + 7) / 8 + 4;  // ... padded to a byte, LEN 0000, NLEN FFFF
+        w.sbytes[s] = uint32_t(bytes);
+        uint32_t crc = w.ccrc[c0];
+        for (int q = 1; q < nch; ++q) {
+            const int64_t lq = min(kChunk, slen - int64_t(q) * kChunk);
+            crc = crc_combine(crc, w.ccrc[c0 + q], uint64_t(lq));
+        }
+        w.scrc[s] = crc;
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(kThr) void dfl_lz_encode_kernel(const uint8_t *__restrict__ in, Geo g, DWs w,
+                                                             uint8_t *__restrict__ out, int cand) {
+    __shared__ uint32_t code[kAll];
+    __shared__ uint32_t wsum[kThr / 64];
+    const int c = blockIdx.x, a = c / g.cpa, k = c - a * g.cpa;
+    const int64_t beg = int64_t(k) * kChunk, len = min(kChunk, g.each - beg);
+    const int s = a * g.spa + int(beg / kSeg);
+    for (int i = threadIdx.x; i < kAll; i += kThr) code[i] = w.scode[int64_t(s) * kAll + i];
+    __syncthreads();
+    const uint8_t *src = in + int64_t(a) * g.each + beg;
+    const int t0 = threadIdx.x * kPerThr;
+    const int n = int(min<int64_t>(kPerThr, max<int64_t>(len - t0, 0)));
+    const bool first = beg + t0 == 0;
+    uint32_t ext[20];
+    load_hist16(src + t0, n > 0 && !first, ext);
+    load64(src, t0, n, ext + 4);
+    const SpanMasks<E> sm = span_masks<E>(ext, n, first, cand);
+    uint32_t bits = 0;
+    parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) {
+        if (!match) {
+            bits += code[span_byte<decltype(e)::value>(ext)] >> 24;
+        } else {
+            int sym, xb;
+            uint32_t xv;
+            len_sym(mlen, sym, xb, xv);
+            bits += (code[sym] >> 24) + uint32_t(xb) + (code[kDOff + dist_sym(D)] >> 24) + uint32_t(dist_xbits(D));
+        }
+    });
+    // exclusive scan of the bit counts over the workgroup
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = bits;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(incl, d);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int q = 0; q < wave; ++q) before += wsum[q];
+    const uint64_t seg_bit0 = w.soff[s] * 8;
+    const uint64_t pos = seg_bit0 + w.cbit[c] + before + incl - bits;
+    uint32_t *o = reinterpret_cast<uint32_t *>(out + a * g.bound);  // slots are 256-byte aligned
+    // first and last word by atomic OR into the zeroed slot, the words between by plain stores
+    if (bits) {
+        const uint64_t w0 = pos >> 5, wl = (pos + bits - 1) >> 5;
+        uint64_t acc = 0;
+        int nacc = int(pos & 31);
+        uint64_t wi = w0;
+        auto add = [&](uint32_t v, int nb) {  // nb <= 20 bits, LSB first
+            acc |= uint64_t(v) << nacc;
+            nacc += nb;
+            if (nacc >= 32) {
+                if (wi == w0 || wi == wl)
+                    atomicOr(o + wi, uint32_t(acc));
+                else
+                    o[wi] = uint32_t(acc);
+                ++wi;
+                acc >>= 32;
+                nacc -= 32;
+            }
+        };
+        parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) {
+            if (!match) {
+                const uint32_t ce = code[span_byte<decltype(e)::value>(ext)];
+                add(ce & 0xFFFFFFu, int(ce >> 24));
+            } else {
+                // length code, its extra bits, distance code, its extra bits
+                int sym, xb;
+                uint32_t xv;
+                len_sym(mlen, sym, xb, xv);
+                const uint32_t cl = code[sym], cd = code[kDOff + dist_sym(D)];
+                add((cl & 0xFFFFFFu) | (xv << (cl >> 24)), int(cl >> 24) + xb);
+                add((cd & 0xFFFFFFu) | (dist_xval(D) << (cd >> 24)), int(cd >> 24) + dist_xbits(D));
+            }
+        });
+        if (nacc > 0) {
+            if (wi == w0 || wi == wl)
+                atomicOr(o + wi, uint32_t(acc));
+            else
+                o[wi] = uint32_t(acc);
+        }
+    }
+    const int64_t sbeg = int64_t(beg / kSeg) * kSeg;
+    if (threadIdx.x == 0 && beg == sbeg) {
+        const uint32_t hb = w.shbits[s];
+        const uint32_t *h = w.shdr + int64_t(s) * kHdrWords;
+        for (uint32_t q = 0; q * 32 < hb; ++q) {
+            const int nb = int(min(32u, hb - q * 32));
+            or_bits(o, seg_bit0 + uint64_t(q) * 32, h[q], nb);
+        }
+    }
+    const int64_t slen = min(kSeg, g.each - sbeg);
+    if (threadIdx.x == kThr - 1 && beg + len == sbeg + slen) {
+        const uint32_t ce = code[256];
+        const uint64_t epos = seg_bit0 + w.cbit[c] + before + incl;
+        or_bits(o, epos, ce & 0xFFFFFFu, int(ce >> 24));
+        const uint64_t end = w.soff[s] + w.sbytes[s];  // byte after FF FF
+        or_bits(o, (end - 2) * 8, 0xFFFFu, 16);
+    }
+}
+
+template <int E>
+void lz_launch(const uint8_t *src, uint8_t *dst, const Geo &g, const DWs &w, int64_t count, uint64_t *sizes,
+               uint32_t *crcs, int cand, hipStream_t st) {
+    const unsigned nc = unsigned(count * g.cpa), ns = unsigned(count * g.spa);
+    hipLaunchKernelGGL(dfl_lz_hist_kernel<E>, dim3(nc), dim3(kThr), 0, st, src, g, w, cand);
+    hipLaunchKernelGGL(dfl_lz_code_kernel, dim3(ns), dim3(kThr), 0, st, g, w);
+    hipLaunchKernelGGL(dfl_scan_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, st, g, w, dst, sizes, crcs,
+                       count);
+    hipLaunchKernelGGL(dfl_lz_encode_kernel<E>, dim3(nc), dim3(kThr), 0, st, src, g, w, dst, cand);
+}
+
 }  // namespace
 
 extern "C" {
@@ -575,6 +1025,68 @@ int ofd_deflate_batch(const void *in, int64_t count, int64_t bytes_each, void *o
     hipLaunchKernelGGL(dfl_scan_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, st, g, w, dst, sizes, crcs,
                        count);
     hipLaunchKernelGGL(dfl_encode_kernel, dim3(nc), dim3(kThr), 0, st, src, g, w, dst);
+    e = hipGetLastError();
+    return e == hipSuccess ? OFD_FW_OK : int(e);
+}
+
+size_t ofd_deflate_lz_bound(int64_t bytes_each) {
+    // The worst token decides.  A literal costs <= 15 bits for 1 byte.  A match
+    // costs <= 15 (length code) + 5 (length extra bits) + 15 (distance code) +
+    // 2 (extra bits of distance 16, the largest candidate) = 37 bits for
+    // >= kMinMatch = 3 bytes, i.e. <= 12.4 bits per byte.  So 15 bits per byte
+    // bounds the codes as in the literal mode, the header (<= 2283 bits) fits
+    // the same kHdrWords, and the slot is the literal mode's.
+    return ofd_deflate_bound(bytes_each);
+}
+
+size_t ofd_deflate_lz_workspace_bytes(int64_t count, int64_t bytes_each) {
+    if (count <= 0 || bytes_each <= 0) return 0;
+    return lz_ws_bytes(count, bytes_each);
+}
+
+int ofd_deflate_lz_set_candidates(int mask) {
+    if (mask < 0 || mask > 3) return OFD_FW_EINVAL;
+    g_lz_cand = mask;
+    return OFD_FW_OK;
+}
+
+int ofd_deflate_lz_batch(const void *in, int64_t count, int64_t bytes_each, int elem_bytes, void *out, uint64_t *sizes,
+                         uint32_t *crcs, void *workspace, size_t workspace_bytes, void *stream) {
+    if (count < 0 || bytes_each < 0) return OFD_FW_EINVAL;
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return OFD_FW_EINVAL;
+    if (count == 0) return OFD_FW_OK;
+    if (!out || !sizes || !crcs || (bytes_each > 0 && !in)) return OFD_FW_EINVAL;
+    if (reinterpret_cast<uintptr_t>(out) & 255u) return OFD_FW_EALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Geo g;
+    g.each = bytes_each;
+    g.cpa = int((bytes_each + kChunk - 1) / kChunk);
+    g.spa = int((bytes_each + kSeg - 1) / kSeg);
+    g.bound = int64_t(ofd_deflate_lz_bound(bytes_each));
+    if (int64_t(count) * g.cpa >= (int64_t(1) << 31)) return OFD_FW_ETOOBIG;
+    if (bytes_each > 0 &&
+        (!workspace || workspace_bytes < lz_ws_bytes(count, bytes_each) || (reinterpret_cast<uintptr_t>(workspace) & 255u)))
+        return OFD_FW_EWORKSPACE;
+    hipError_t e = hipMemsetAsync(out, 0, size_t(count) * size_t(g.bound), st);
+    if (e != hipSuccess) return int(e);
+    uint8_t *dst = static_cast<uint8_t *>(out);
+    if (bytes_each == 0) {  // an empty array: the final block alone
+        hipLaunchKernelGGL(dfl_scan_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, st, g, DWs{}, dst, sizes,
+                           crcs, count);
+        e = hipGetLastError();
+        return e == hipSuccess ? OFD_FW_OK : int(e);
+    }
+    const DWs w = lz_carve(workspace, count, g);
+    e = hipMemsetAsync(w.shist, 0, size_t(count) * g.spa * 4 * kAll, st);
+    if (e != hipSuccess) return int(e);
+    const uint8_t *src = static_cast<const uint8_t *>(in);
+    const int cand = g_lz_cand;
+    switch (elem_bytes) {
+        case 1: lz_launch<1>(src, dst, g, w, count, sizes, crcs, cand, st); break;
+        case 2: lz_launch<2>(src, dst, g, w, count, sizes, crcs, cand, st); break;
+        case 4: lz_launch<4>(src, dst, g, w, count, sizes, crcs, cand, st); break;
+        default: lz_launch<8>(src, dst, g, w, count, sizes, crcs, cand, st); break;
+    }
     e = hipGetLastError();
     return e == hipSuccess ? OFD_FW_OK : int(e);
 }

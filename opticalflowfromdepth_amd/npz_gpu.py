@@ -16,6 +16,9 @@ host:
 The files are ordinary zips that np.load / zipfile read and CRC-check; the
 arrays come back bit for bit.  The compressed bytes differ from zlib's (no
 LZ77 matches: ~2.3x on these planes against zlib level 6's ~2.9x).
+``GpuNpzWriter(matches=True)`` (``--writer gpu-lz``) uses the encoder's match
+mode instead (ofd_deflate_lz_batch: matches at the element stride), opt-in:
+about 12 % fewer bytes per image, the deflate call 7-12 % slower.
 """
 from __future__ import annotations
 
@@ -181,7 +184,9 @@ class GpuNpzWriter:
     stream therefore keeps its queue full (augmentations already queued on
     it, or on side streams, keep running while earlier files deflate)."""
 
-    def __init__(self, workers: int = 8, header_level: int = 6, max_pending_bytes: int = 8 << 30):
+    def __init__(self, workers: int = 8, header_level: int = 6, max_pending_bytes: int = 8 << 30,
+                 matches: bool = False):
+        self.matches = bool(matches)  # ofd_deflate_lz_batch (LZ77 matches at the element stride) instead of literals
         self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="gnpz")
         # one fetch thread: waits for each batch's deflate, then for room under
         # max_pending_bytes, then copies the streams; it never occupies a
@@ -228,18 +233,23 @@ class GpuNpzWriter:
             return
         lib = _native.lib()
         each = int(x[0].numel() * x.element_size())
-        bound = int(lib.ofd_deflate_bound(each))
+        lz = self.matches
+        bound = int((lib.ofd_deflate_lz_bound if lz else lib.ofd_deflate_bound)(each))
         dev = x.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             out = torch.empty(count * bound, dtype=torch.uint8, device=dev)
             sizes = torch.empty(count, dtype=torch.int64, device=dev)
             crcs = torch.empty(count, dtype=torch.int32, device=dev)
-            nws = int(lib.ofd_deflate_workspace_bytes(count, each))
+            nws = int((lib.ofd_deflate_lz_workspace_bytes if lz else lib.ofd_deflate_workspace_bytes)(count, each))
             ws = self._workspace(dev, stream, nws) if nws else None
-            rc = lib.ofd_deflate_batch(x.data_ptr(), count, each, out.data_ptr(), sizes.data_ptr(), crcs.data_ptr(),
-                                       ws.data_ptr() if ws is not None else None, nws, stream.cuda_stream)
-            _native.check(rc, "ofd_deflate_batch")
+            tail = (out.data_ptr(), sizes.data_ptr(), crcs.data_ptr(), ws.data_ptr() if ws is not None else None, nws,
+                    stream.cuda_stream)
+            if lz:
+                rc = lib.ofd_deflate_lz_batch(x.data_ptr(), count, each, x.element_size(), *tail)
+            else:
+                rc = lib.ofd_deflate_batch(x.data_ptr(), count, each, *tail)
+            _native.check(rc, "ofd_deflate_lz_batch" if lz else "ofd_deflate_batch")
             sz_h = torch.empty(count, dtype=torch.int64, pin_memory=True)
             cr_h = torch.empty(count, dtype=torch.int32, pin_memory=True)
             sz_h.copy_(sizes, non_blocking=True)

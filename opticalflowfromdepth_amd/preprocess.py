@@ -739,13 +739,17 @@ def image_complete(d: str, schedule: Sequence[int] = AUGMENT_SCHEDULE, augment: 
     return all(zip_complete(os.path.join(d, n)) for n in names)
 
 
+WRITER_KINDS = ["gpu", "gpu-lz", "zlib", "sync"]
+
+
 def make_writer(kind: str):
     """--writer: ``gpu`` (default) deflates on the GPU (npz_gpu.GpuNpzWriter),
+    ``gpu-lz`` the same with the encoder's match mode (smaller files, opt-in),
     ``zlib`` a 16-thread host zlib pool (NpzWriter, numpy's level 6),
     ``sync`` the reference's synchronous np.savez_compressed (preprocess.py:446)."""
-    if kind == "gpu":
+    if kind in ("gpu", "gpu-lz"):
         from .npz_gpu import GpuNpzWriter
-        return GpuNpzWriter(workers=int(os.environ.get("OFD_WRITER_WORKERS", "8")))
+        return GpuNpzWriter(workers=int(os.environ.get("OFD_WRITER_WORKERS", "8")), matches=kind == "gpu-lz")
     if kind == "zlib":
         return NpzWriter(int(os.environ.get("OFD_WRITER_WORKERS", "16")), 6)
     if kind == "sync":
@@ -786,7 +790,7 @@ def main(argv=None) -> dict:
                     help="images per batched call (larger batches amortise the hole-fill latency; the writer "
                          "bounds the product at any batch)")
     ap.add_argument("--out", default="datasets/AugmentedDatasets/synthetic")
-    ap.add_argument("--writer", default="gpu", choices=["gpu", "zlib", "sync"])
+    ap.add_argument("--writer", default="gpu", choices=WRITER_KINDS)
     ap.add_argument("--skip-existing", action="store_true", help="resume: skip images whose 121 files exist")
     ap.add_argument("--no-augment", action="store_true")
     ap.add_argument("--no-save", action="store_true")

@@ -7,7 +7,8 @@ usage: python tools/pipeline_time.py [B H W] [--save MODE ...] [--dir D]
   MODE: none (compute only), sync (np.savez_compressed in the caller, the
   reference's way, preprocess.py:446/:471), poolN:L (NpzWriter with N threads
   at zlib level L; 6 = numpy's level), gpuN (GpuNpzWriter: arrays deflated on
-  the GPU, N host threads assemble and write the zips).
+  the GPU, N host threads assemble and write the zips), gpulzN (the same
+  with the encoder's match mode, GpuNpzWriter(matches=True)).
 """
 import argparse
 import os
@@ -51,7 +52,8 @@ for mode in args.save:
     ppa._streams = _warm._streams  # the warmed streams (their workspaces are cached per stream)
     if mode.startswith("gpu"):
         from opticalflowfromdepth_amd.npz_gpu import GpuNpzWriter
-        ppa.writer = GpuNpzWriter(workers=int(mode[3:] or 8))
+        lz = mode.startswith("gpulz")
+        ppa.writer = GpuNpzWriter(workers=int(mode[5 if lz else 3:] or 8), matches=lz)
     out = None
     if mode != "none":
         base = tempfile.mkdtemp(prefix="ppa_", dir=root)
