@@ -42,8 +42,10 @@ int ofd_deflate_batch(const void *in, int64_t count, int64_t bytes_each, void *o
  * stride.  Every 64-byte span is parsed greedily: the longest run of bytes
  * equal to the byte D before them, D in {1, elem_bytes, 2 * elem_bytes}, is
  * coded as a match when it is 3 bytes or longer and stays inside the span.
- * Same stream format, slots, sizes, CRCs and return codes as above; the
- * streams are smaller wherever the data repeats at those distances. */
+ * Same stream format, slots, sizes, CRCs and return codes as above (one set of
+ * kernels serves both modes; a segment in which nothing matches is byte for
+ * byte ofd_deflate_batch's block); the streams are smaller wherever the data
+ * repeats at those distances. */
 
 /* Output slot bytes per array (a multiple of 256). */
 size_t ofd_deflate_lz_bound(int64_t bytes_each);

@@ -8,37 +8,40 @@
 // zipfile, np.load) reads:
 //
 //   * every array is cut into 1 MiB SEGMENTS; each segment is one dynamic-
-//     Huffman deflate block (literals only: 256 byte symbols + end-of-block,
-//     no LZ77 matches -- f64 planes of f32 / integer values are dominated by
-//     zero bytes, which a per-segment code prices at about one bit), closed
-//     by an empty stored block (zlib's Z_SYNC_FLUSH marker 00 00 FF FF), so
-//     every segment ends on a byte boundary and the segments concatenate;
+//     Huffman deflate block, closed by an empty stored block (zlib's
+//     Z_SYNC_FLUSH marker 00 00 FF FF), so every segment ends on a byte
+//     boundary and the segments concatenate;
 //   * the array's stream ends with an empty final fixed block (03 00);
 //   * CRC-32 (zlib's polynomial) of every array, for the zip headers.
 //
+// Two modes share every kernel; they differ in how a thread's 64-byte span
+// becomes tokens and in the width of the symbol tables:
+//   literal (ofd_deflate_batch)  every byte is a literal: 256 byte symbols +
+//          end of block.  f64 planes of f32 / integer values are dominated
+//          by zero bytes, which a per-segment code prices at about one bit.
+//   match (ofd_deflate_lz_batch, opt-in)  every thread parses its span
+//          greedily for runs equal to the bytes 1, E or 2E back (E = the
+//          element size): 286 literal / length and 30 distance symbols.
+//
 // Kernels (all on the caller's stream, no host synchronisation):
-//   HIST   one workgroup per 16 KiB chunk: the chunk's byte histogram (kept
-//          per chunk and added into its segment's), and the chunk's CRC-32
-//          (a table CRC per thread over 64 bytes, folded by x^(8n) mod P).
+//   HIST   one workgroup per 16 KiB chunk: the histogram of the chunk's
+//          symbols (kept per chunk and added into its segment's), its
+//          matches' extra bits, and the chunk's CRC-32 (a table CRC per
+//          thread over 64 bytes, folded by x^(8n) mod P).
 //   CODE   one workgroup per segment: the Huffman code lengths (max 15; the
-//          frequencies are flattened and the tree rebuilt until it fits),
-//          the canonical codes, the block header (code-length code, 257
-//          literal / end lengths, one zero distance length), the segment's
-//          size in bytes, every chunk's bit offset, the segment CRC.
+//          frequencies are flattened and the tree rebuilt until it fits) of
+//          the literal / length tree and, if the segment has a match, the
+//          distance tree, the canonical codes, the block header (code-length
+//          code, HLIT literal / length lengths, HDIST distance lengths: 257
+//          and one zero length without a match), the segment's size in
+//          bytes, every chunk's bit offset, the segment CRC.
 //   SCAN   one thread per array: segment offsets, the array's size, its CRC,
 //          the final block.
-//   ENCODE one workgroup per chunk: per-thread bit counts, a block scan, then
-//          every thread ORs its codes into the (zeroed) output with 32-bit
-//          atomics; the chunk holding a segment's start writes the header,
-//          the one holding its end the end-of-block code and FF FF.
-//
-// ofd_deflate_lz_batch (opt-in, second half of this file) is the same
-// structure with LZ77 matches: every thread parses its 64-byte span greedily
-// for runs equal to the bytes 1, E or 2E back (E = the element size), HIST
-// counts 286 literal / length and 30 distance symbols plus the matches' extra
-// bits, CODE builds two trees and sends HLIT / HDIST, ENCODE runs the same
-// parse again and emits the tokens.  ofd_deflate_batch and its bytes do not
-// change.
+//   ENCODE one workgroup per chunk: the same tokens again, per-thread bit
+//          counts, a block scan, then every thread packs its codes into
+//          32-bit words of the (zeroed) output; the chunk holding a segment's
+//          start writes the header, the one holding its end the end-of-block
+//          code and FF FF.
 //
 // Plain HIP for gfx950.
 
@@ -59,9 +62,26 @@ constexpr int kPerThr = int(kChunk / kThr);     // 64 bytes per thread
 constexpr int64_t kSeg = int64_t(1) << 20;      // bytes per deflate block
 constexpr int kChunksPerSeg = int(kSeg / kChunk);
 constexpr int kSym = 257;                       // literals 0..255 + end of block
+constexpr int kLSym = 286;                      // ... + 29 length symbols
+constexpr int kDSym = 30;                       // distance symbols
+constexpr int kDOff = kLSym;                    // the distance symbols follow in the joint tables ...
+constexpr int kAll = 320;                       // ... of 316 entries, padded
 constexpr int kMaxLen = 15;
-constexpr int kHdrWords = 80;                   // block header bits (<= 3+5+5+4+57+258*7 = 1880)
+constexpr int kMinMatch = 3;
+constexpr int kCandDefault = 3;                 // bit 0: distance 1, bit 1: distance 2E (E itself always)
+constexpr int kHdrWords = 80;                   // block header words
 constexpr uint32_t kPoly = 0xEDB88320u;         // CRC-32, reflected
+static_assert(kPerThr == 64, "a span's equality masks are 64-bit");
+// BFINAL BTYPE HLIT HDIST HCLEN, 19 code-length-code lengths, 316 lengths of <= 7 bits: 2283 bits (match mode)
+static_assert(14 + 19 * 3 + (kLSym + kDSym) * 7 <= kHdrWords * 32, "the block header must fit kHdrWords");
+
+// Table widths of a mode: symbol counts per chunk and per segment, codes per
+// segment.  The literal mode keeps no count for the end of block (one per
+// segment) and none for the match symbols it never codes.
+constexpr int hist_width(bool match) { return match ? kAll : 256; }
+constexpr int code_width(bool match) { return match ? kAll : kSym; }
+
+int g_lz_cand = kCandDefault;
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -104,42 +124,50 @@ struct Geo {        // one batch of `count` arrays of `each` bytes
 };
 
 struct DWs {
-    uint16_t *chist;   // [chunks][256]
+    uint16_t *chist;   // [chunks][hist_width]
     uint32_t *ccrc;    // [chunks]
+    uint32_t *cxb;     // [chunks] extra bits of the chunk's matches (match mode only)
     uint64_t *cbit;    // [chunks] bit offset of the chunk's first code from the segment start
-    uint32_t *shist;   // [segs][256]  (zeroed per call)
-    uint32_t *scode;   // [segs][257]  bit-reversed code | len << 24
+    uint32_t *shist;   // [segs][hist_width]  (zeroed per call)
+    uint32_t *scode;   // [segs][code_width]  bit-reversed code | len << 24
     uint32_t *shdr;    // [segs][kHdrWords]
     uint32_t *shbits;  // [segs] header bits
     uint32_t *sbytes;  // [segs] segment bytes (header .. FF FF)
     uint32_t *scrc;    // [segs]
     uint64_t *soff;    // [segs] byte offset of the segment in its array's slot
-    uint32_t *cxb;     // [chunks] extra bits of the chunk's matches (match mode only)
 };
 
-size_t ws_bytes(int64_t count, int64_t each) {
-    const int64_t cpa = (each + kChunk - 1) / kChunk, spa = (each + kSeg - 1) / kSeg;
-    const size_t nc = size_t(count * cpa), ns = size_t(count * spa);
-    return align256(nc * 512) + align256(nc * 4) + align256(nc * 8) + align256(ns * 1024) + align256(ns * 4 * kSym) +
-           align256(ns * 4 * kHdrWords) + 4 * align256(ns * 4) + align256(ns * 8);
+// The workspace of a call on nc chunks and ns segments: its arrays carved from
+// ws into w (ws == nullptr: none) and its size in bytes.
+size_t ws_layout(void *ws, size_t nc, size_t ns, bool match, DWs *w) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        void *p = ws ? static_cast<char *>(ws) + off : nullptr;
+        off += align256(bytes);
+        return p;
+    };
+    const size_t hw = size_t(hist_width(match)), cw = size_t(code_width(match));
+    DWs d{};
+    d.chist = static_cast<uint16_t *>(take(nc * 2 * hw));
+    d.ccrc = static_cast<uint32_t *>(take(nc * 4));
+    if (match) d.cxb = static_cast<uint32_t *>(take(nc * 4));
+    d.cbit = static_cast<uint64_t *>(take(nc * 8));
+    d.shist = static_cast<uint32_t *>(take(ns * 4 * hw));
+    d.scode = static_cast<uint32_t *>(take(ns * 4 * cw));
+    d.shdr = static_cast<uint32_t *>(take(ns * 4 * kHdrWords));
+    d.shbits = static_cast<uint32_t *>(take(ns * 4));
+    d.sbytes = static_cast<uint32_t *>(take(ns * 4));
+    d.scrc = static_cast<uint32_t *>(take(ns * 4));
+    // one more per-segment word, unused: ofd_deflate_workspace_bytes has always counted it, and callers hold that size
+    if (!match) take(ns * 4);
+    d.soff = static_cast<uint64_t *>(take(ns * 8));
+    if (w) *w = d;
+    return off;
 }
 
-DWs carve(void *ws, int64_t count, const Geo &g) {
-    const size_t nc = size_t(count) * g.cpa, ns = size_t(count) * g.spa;
-    char *p = static_cast<char *>(ws);
-    DWs w;
-    w.chist = reinterpret_cast<uint16_t *>(p), p += align256(nc * 512);
-    w.ccrc = reinterpret_cast<uint32_t *>(p), p += align256(nc * 4);
-    w.cbit = reinterpret_cast<uint64_t *>(p), p += align256(nc * 8);
-    w.shist = reinterpret_cast<uint32_t *>(p), p += align256(ns * 1024);
-    w.scode = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kSym);
-    w.shdr = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kHdrWords);
-    w.shbits = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
-    w.sbytes = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
-    w.scrc = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
-    w.soff = reinterpret_cast<uint64_t *>(p);
-    w.cxb = nullptr;
-    return w;
+size_t ws_bytes(int64_t count, int64_t each, bool match) {
+    const int64_t cpa = (each + kChunk - 1) / kChunk, spa = (each + kSeg - 1) / kSeg;
+    return ws_layout(nullptr, size_t(count * cpa), size_t(count * spa), match, nullptr);
 }
 
 __device__ __forceinline__ void make_crc_table(uint32_t *T) {
@@ -175,39 +203,199 @@ __device__ __forceinline__ void load64(const uint8_t *__restrict__ src, int t0, 
     }
 }
 
+// ---------------------------------------------------------------- tokens
+// A thread turns its 64-byte span into tokens, in HIST and again in ENCODE (no
+// token is ever stored).  Template parameter E is the mode.  E = 0, the literal
+// mode: every byte is a literal.  E = 1, 2, 4, 8, the match mode at that
+// element size: at byte p the thread takes the longest run b[p+i] == b[p+i-D]
+// over the candidate distances D in {1, E, 2E} (the smaller D on ties) that
+// stays inside the span, and codes it as a match when it is kMinMatch bytes or
+// more, else b[p] as a literal.  A match may read the 2E <= 16 bytes before
+// the span (they are input too), never bytes before its own array.  The parse
+// is a pure function of the span and those 16 bytes.
+
+// The 16 bytes before a span (zeros when there are none to read)
+__device__ __forceinline__ void load_hist16(const uint8_t *p, bool have, uint32_t hs[4]) {
+    hs[0] = hs[1] = hs[2] = hs[3] = 0u;
+    if (!have) return;
+    const uint8_t *h = p - 16;
+    if ((reinterpret_cast<uintptr_t>(h) & 15u) == 0) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(h);
+        hs[0] = v.x, hs[1] = v.y, hs[2] = v.z, hs[3] = v.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) hs[q] |= uint32_t(h[4 * q + r]) << (8 * r);
+    }
+}
+
+// ext = 16 history bytes then the span's 64, as 20 little-endian words.
+// Bit i of the result: span byte i equals the byte D before it.
+template <int D, int q>
+__device__ __forceinline__ uint64_t eq_nibble(const uint32_t ext[20]) {  // the mask's bits 4q .. 4q + 3
+    uint32_t prev;
+    if constexpr (D % 4 == 0)
+        prev = ext[4 + q - D / 4];
+    else
+        prev = uint32_t(((uint64_t(ext[4 + q]) << 32) | ext[3 + q]) >> (8 * (4 - D)));
+    const uint32_t x = ext[4 + q] ^ prev;
+    uint32_t t = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);  // 0x80 in every zero byte of x
+    t >>= 7;
+    return uint64_t((t | (t >> 7) | (t >> 14) | (t >> 21)) & 0xFu) << (4 * q);
+}
+
+template <int D, int... Q>
+__device__ __forceinline__ uint64_t eq_mask_seq(const uint32_t ext[20], std::integer_sequence<int, Q...>) {
+    return (eq_nibble<D, Q>(ext) | ...);
+}
+
+template <int D>
+__device__ __forceinline__ uint64_t eq_mask(const uint32_t ext[20]) {
+    static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16, "distance");
+    return eq_mask_seq<D>(ext, std::make_integer_sequence<int, 16>{});
+}
+
+// RFC 1951 3.2.5 for the distances in use (powers of two up to 16)
+__device__ __forceinline__ constexpr int dist_sym(int D) { return D == 1 ? 0 : D == 2 ? 1 : D == 4 ? 3 : D == 8 ? 5 : 7; }
+__device__ __forceinline__ constexpr int dist_xbits(int D) { return D == 8 ? 1 : D == 16 ? 2 : 0; }
+__device__ __forceinline__ constexpr uint32_t dist_xval(int D) { return D == 8 ? 1u : D == 16 ? 3u : 0u; }
+
+// length 3..257 -> symbol, extra bit count and value (258 is never emitted: a span has 64 bytes)
+__device__ __forceinline__ void len_sym(int len, int &sym, int &xb, uint32_t &xv) {
+    const int x = len - 3;
+    if (x < 8) {
+        sym = 257 + x, xb = 0, xv = 0u;
+    } else {
+        const int k = 29 - __clz(x);  // 8..15: 1 extra bit, 16..31: 2, 32..63: 3, ...
+        sym = 257 + 4 * (k + 1) + ((x >> k) & 3), xb = k, xv = uint32_t(x) & ((1u << k) - 1u);
+    }
+}
+
+template <int E>
+struct SpanMasks {
+    uint64_t m1, me, m2;  // distance 1 (E > 1 only), E, 2E; unused in the literal mode
+};
+
+// n = the span's bytes, first = the span starts its array (no history to match)
+template <int E>
+__device__ __forceinline__ SpanMasks<E> span_masks(const uint32_t ext[20], int n, bool first, int cand) {
+    SpanMasks<E> m{0, 0, 0};
+    if constexpr (E != 0) {
+        const uint64_t live = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+        if (E > 1 && (cand & 1)) m.m1 = eq_mask<1>(ext) & live & (first ? ~0ull << 1 : ~0ull);
+        m.me = eq_mask<E>(ext) & live & (first ? ~0ull << E : ~0ull);
+        if (cand & 2) m.m2 = eq_mask<2 * E>(ext) & live & (first ? ~0ull << (2 * E) : ~0ull);
+    }
+    return m;
+}
+
+template <int e, int E, class F>
+__device__ __forceinline__ void parse_step(const SpanMasks<E> &m, int n, int &next, F &tok) {
+    if constexpr (E == 0) {
+        if (e < n) tok(std::integral_constant<int, e>{}, false, 0, 0);
+    } else if (e == next && e < n) {
+        auto run = [](uint64_t x) -> int {
+            const uint64_t y = ~(x >> e);
+            return y ? __builtin_ctzll(y) : 64;
+        };
+        int best = E > 1 ? run(m.m1) : 0, D = 1;
+        const int re = run(m.me), r2 = run(m.m2);
+        if (re > best) best = re, D = E;
+        if (r2 > best) best = r2, D = 2 * E;
+        const bool match = best >= kMinMatch;
+        tok(std::integral_constant<int, e>{}, match, best, D);
+        next = e + (match ? best : 1);
+    }
+}
+
+template <int E, class F, int... I>
+__device__ __forceinline__ void parse_steps(const SpanMasks<E> &m, int n, F &tok, std::integer_sequence<int, I...>) {
+    int next = 0;
+    (parse_step<I, E>(m, n, next, tok), ...);
+}
+
+// tok(e, is_match, length, D) for every token of the span, in order; e is the
+// token's first byte as a std::integral_constant, so that every index into the
+// span's registers is a constant.
+template <int E, class F>
+__device__ __forceinline__ void parse_span(const SpanMasks<E> &m, int n, F &&tok) {
+    parse_steps<E>(m, n, tok, std::make_integer_sequence<int, kPerThr>{});
+}
+
+// byte e of the span in ext (e a constant)
+template <int e>
+__device__ __forceinline__ uint32_t span_byte(const uint32_t ext[20]) {
+    return (ext[4 + (e >> 2)] >> (8 * (e & 3))) & 0xFFu;
+}
+
+// A thread's span of chunk bytes [t0, t0 + n) at src (chunk-relative; the chunk
+// starts at byte beg of its array) with its history, as parse_span wants them
+template <int E>
+__device__ __forceinline__ void load_span(const uint8_t *__restrict__ src, int64_t beg, int t0, int n, uint32_t ext[20]) {
+    if constexpr (E != 0) load_hist16(src + t0, n > 0 && beg + t0 > 0, ext);
+    load64(src, t0, n, ext + 4);
+}
+
 // ---------------------------------------------------------------- HIST
 // chunk c = (array a, chunk k of the array); thread t owns bytes [64 t, 64 t + 64)
-__global__ __launch_bounds__(kThr) void dfl_hist_kernel(const uint8_t *__restrict__ in, Geo g, DWs w) {
+template <int E>
+__global__ __launch_bounds__(kThr) void dfl_hist_kernel(const uint8_t *__restrict__ in, Geo g, DWs w, int cand) {
+    constexpr int kHist = hist_width(E != 0);
     __shared__ uint32_t T[256];
-    __shared__ uint32_t H[256];
+    __shared__ uint32_t H[kHist];
     __shared__ uint32_t C[kThr];
+    __shared__ uint32_t X;
     const int c = blockIdx.x, a = c / g.cpa, k = c - a * g.cpa;
     const int64_t beg = int64_t(k) * kChunk, len = min(kChunk, g.each - beg);
     const uint8_t *src = in + int64_t(a) * g.each + beg;
     make_crc_table(T);
-    H[threadIdx.x] = 0u;
+    for (int i = threadIdx.x; i < kHist; i += kThr) H[i] = 0u;
+    if (threadIdx.x == 0) X = 0u;
     __syncthreads();
     const int t0 = threadIdx.x * kPerThr;
     const int n = int(min<int64_t>(kPerThr, max<int64_t>(len - t0, 0)));
-    uint32_t wd[16];
-    load64(src, t0, n, wd);
-    uint32_t crc = 0xFFFFFFFFu, zeros = 0;
+    uint32_t ext[20];
+    load_span<E>(src, beg, t0, n, ext);
+    uint32_t crc = 0xFFFFFFFFu;
+    auto crc_byte = [&](uint32_t b) { crc = T[(crc ^ b) & 0xFFu] ^ (crc >> 8); };
+    // A match skips bytes, so the match mode's CRC takes a pass of its own; in
+    // the literal mode every byte is a token and its CRC step rides along (a
+    // second pass there costs 46 spilled SGPRs and a wave per SIMD).
+    if constexpr (E != 0) {
 #pragma unroll
-    for (int e = 0; e < kPerThr; ++e) {
-        if (e < n) {
-            const uint32_t b = (wd[e >> 2] >> (8 * (e & 3))) & 0xFFu;
-            crc = T[(crc ^ b) & 0xFFu] ^ (crc >> 8);
+        for (int e = 0; e < kPerThr; ++e)
+            if (e < n) crc_byte(ext[4 + (e >> 2)] >> (8 * (e & 3)));
+    }
+    uint32_t zeros = 0, xbits = 0;
+    const SpanMasks<E> sm = span_masks<E>(ext, n, beg + t0 == 0, cand);
+    parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) {
+        if (!match) {
+            const uint32_t b = span_byte<decltype(e)::value>(ext);
+            if constexpr (E == 0) crc_byte(b);
             if (b == 0u)
                 ++zeros;
             else
                 atomicAdd(&H[b], 1u);
+        } else {
+            int sym, xb;
+            uint32_t xv;
+            len_sym(mlen, sym, xb, xv);
+            atomicAdd(&H[sym], 1u);
+            atomicAdd(&H[kDOff + dist_sym(D)], 1u);
+            xbits += uint32_t(xb + dist_xbits(D));
         }
+    });
+    // zero literals dominate: one wave sum instead of 64 colliding LDS atomics per lane-step
+    for (int d = 32; d > 0; d >>= 1) {
+        zeros += __shfl_xor(zeros, d);
+        if constexpr (E != 0) xbits += __shfl_xor(xbits, d);
     }
-    crc = ~crc;
-    // zero bytes dominate: one wave sum instead of 64 colliding LDS atomics per lane-step
-    for (int d = 32; d > 0; d >>= 1) zeros += __shfl_xor(zeros, d);
-    if ((threadIdx.x & 63) == 0 && zeros) atomicAdd(&H[0], zeros);
-    C[threadIdx.x] = crc;
+    if ((threadIdx.x & 63) == 0) {
+        if (zeros) atomicAdd(&H[0], zeros);
+        if (xbits) atomicAdd(&X, xbits);
+    }
+    C[threadIdx.x] = ~crc;
     __syncthreads();
     // fold the per-thread CRCs (thread t covers n_t bytes, all 64 but a ragged tail)
     for (int s = 1; s < kThr; s <<= 1) {
@@ -218,10 +406,15 @@ __global__ __launch_bounds__(kThr) void dfl_hist_kernel(const uint8_t *__restric
         __syncthreads();
     }
     const int seg = a * g.spa + int(beg / kSeg);
-    const uint32_t h = H[threadIdx.x];
-    w.chist[int64_t(c) * 256 + threadIdx.x] = uint16_t(h);
-    if (h) atomicAdd(&w.shist[int64_t(seg) * 256 + threadIdx.x], h);
-    if (threadIdx.x == 0) w.ccrc[c] = len > 0 ? C[0] : 0u;
+    for (int i = threadIdx.x; i < kHist; i += kThr) {
+        const uint32_t h = H[i];
+        w.chist[int64_t(c) * kHist + i] = uint16_t(h);
+        if (h) atomicAdd(&w.shist[int64_t(seg) * kHist + i], h);
+    }
+    if (threadIdx.x == 0) {
+        w.ccrc[c] = len > 0 ? C[0] : 0u;
+        if constexpr (E != 0) w.cxb[c] = X;
+    }
 }
 
 // ---------------------------------------------------------------- CODE
@@ -336,441 +529,14 @@ __device__ __forceinline__ void put_bits(uint32_t *buf, uint32_t &pos, uint32_t 
         if ((v >> b) & 1u) buf[pos >> 5] |= 1u << (pos & 31);
 }
 
-__global__ __launch_bounds__(kThr) void dfl_code_kernel(Geo g, DWs w) {
-    __shared__ HuffLds L;
-    __shared__ uint32_t f[512];
-    __shared__ uint32_t code[kSym];
-    __shared__ uint32_t hdr[kHdrWords];
-    __shared__ uint32_t clf[19];
-    __shared__ uint32_t clcode[19];
-    __shared__ uint64_t cb[kChunksPerSeg];
-    const int s = blockIdx.x, a = s / g.spa, k = s - a * g.spa;
-    const int64_t sbeg = int64_t(k) * kSeg, slen = min(kSeg, g.each - sbeg);
-    const int c0 = a * g.cpa + int(sbeg / kChunk), nch = int((slen + kChunk - 1) / kChunk);
-    for (int i = threadIdx.x; i < 512; i += kThr) f[i] = i < 256 ? w.shist[int64_t(s) * 256 + i] : (i == 256 ? 1u : 0u);
-    for (int i = threadIdx.x; i < kHdrWords; i += kThr) hdr[i] = 0u;
-    __syncthreads();
-    // the data's own frequencies are kept for the sizes below (f is flattened)
-    const uint32_t fdata = threadIdx.x < 256 ? f[threadIdx.x] : 0u;
-    huff_lengths(f, kSym, kMaxLen, L);
-    if (threadIdx.x == 0) canonical(L.len, kSym, code);
-    __syncthreads();
-    // code-length code: frequencies of the 258 transmitted lengths (257 + one zero distance length)
-    uint8_t litlen = threadIdx.x < kSym ? L.len[threadIdx.x] : 0;
-    const uint8_t eob_len = L.len[256];
-    __syncthreads();
-    if (threadIdx.x < 19) clf[threadIdx.x] = 0u;
-    __syncthreads();
-    if (threadIdx.x < kSym) atomicAdd(&clf[litlen], 1u);
-    if (threadIdx.x == 0) atomicAdd(&clf[0], 1u);  // the distance length
-    if (threadIdx.x == 0) atomicAdd(&clf[L.len[256]], 1u);
-    __syncthreads();
-    // (symbol 256 is past the 256 threads above: counted by thread 0)
-    huff_lengths(clf, 19, 7, L);
-    if (threadIdx.x == 0) {
-        canonical(L.len, 19, clcode);
-        // block header: BFINAL 0, BTYPE 2 (dynamic), HLIT 257, HDIST 1, HCLEN
-        static const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        int hclen = 19;
-        while (hclen > 4 && L.len[order[hclen - 1]] == 0) --hclen;
-        uint32_t pos = 0;
-        put_bits(hdr, pos, 0u, 1);
-        put_bits(hdr, pos, 2u, 2);
-        put_bits(hdr, pos, 0u, 5);   // HLIT - 257
-        put_bits(hdr, pos, 0u, 5);   // HDIST - 1
-        put_bits(hdr, pos, uint32_t(hclen - 4), 4);
-        for (int i = 0; i < hclen; ++i) put_bits(hdr, pos, L.len[order[i]], 3);
-        for (int sy = 0; sy <= kSym; ++sy) {  // 257 literal / end lengths, then the distance length 0
-            const uint32_t l = sy < kSym ? (code[sy] >> 24) : 0u;
-            put_bits(hdr, pos, clcode[l] & 0xFFFFFFu, int(clcode[l] >> 24));
-        }
-        w.shbits[s] = pos;
-    }
-    __syncthreads();
-    (void)eob_len;
-    for (int i = threadIdx.x; i < kHdrWords; i += kThr) w.shdr[int64_t(s) * kHdrWords + i] = hdr[i];
-    for (int i = threadIdx.x; i < kSym; i += kThr) w.scode[int64_t(s) * kSym + i] = code[i];
-    // chunk bit counts from the chunk histograms (thread t: symbol t's length),
-    // in order: each chunk's first code sits after the header and the chunks before it
-    const uint32_t mylen = threadIdx.x < 256 ? (code[threadIdx.x] >> 24) : 0u;
-    for (int q = 0; q < nch; ++q) {
-        uint32_t bits = uint32_t(w.chist[int64_t(c0 + q) * 256 + threadIdx.x]) * mylen;
-        for (int d = 32; d > 0; d >>= 1) bits += __shfl_xor(bits, d);
-        if (threadIdx.x == 0) cb[q] = 0;
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&cb[q]), (unsigned long long)bits);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        uint64_t acc = w.shbits[s];
-        for (int q = 0; q < nch; ++q) {
-            const uint64_t b = cb[q];
-            w.cbit[c0 + q] = acc;
-            acc += b;
-        }
-        acc += code[256] >> 24;                 // end of block
-        acc += 3;                               // sync flush: an empty stored block's header ...
-        const uint64_t bytes = (acc + 7) / 8 + 4;  // ... padded to a byte, LEN 0000, NLEN FFFF
-        w.sbytes[s] = uint32_t(bytes);
-        // segment CRC from its chunks' CRCs
-        uint32_t crc = w.ccrc[c0];
-        for (int q = 1; q < nch; ++q) {
-            const int64_t lq = min(kChunk, slen - int64_t(q) * kChunk);
-            crc = crc_combine(crc, w.ccrc[c0 + q], uint64_t(lq));
-        }
-        w.scrc[s] = crc;
-    }
-    (void)fdata;
-}
-
-// ---------------------------------------------------------------- SCAN
-__global__ void dfl_scan_kernel(Geo g, DWs w, uint8_t *__restrict__ out, uint64_t *__restrict__ sizes,
-                                uint32_t *__restrict__ crcs, int64_t count) {
-    const int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (a >= count) return;
-    uint64_t off = 0;
-    uint32_t crc = 0;
-    for (int k = 0; k < g.spa; ++k) {
-        const int64_t s = a * g.spa + k;
-        w.soff[s] = off;
-        off += w.sbytes[s];
-        const int64_t lk = min(kSeg, g.each - int64_t(k) * kSeg);
-        crc = k == 0 ? w.scrc[s] : crc_combine(crc, w.scrc[s], uint64_t(lk));
-    }
-    uint8_t *o = out + a * g.bound;
-    o[off] = 0x03;  // final empty fixed block: BFINAL 1, BTYPE 1, end of block
-    o[off + 1] = 0x00;
-    sizes[a] = off + 2;
-    crcs[a] = g.spa ? crc : 0u;
-}
-
-// ---------------------------------------------------------------- ENCODE
-__device__ __forceinline__ void or_bits(uint32_t *o, uint64_t pos, uint64_t v, int n) {  // n <= 32, into zeroed memory
-    const uint64_t wd = pos >> 5;
-    const int sh = int(pos & 31);
-    const uint64_t x = (v & ((n == 32) ? 0xFFFFFFFFull : ((1ull << n) - 1))) << sh;
-    if (uint32_t(x)) atomicOr(o + wd, uint32_t(x));
-    if (uint32_t(x >> 32)) atomicOr(o + wd + 1, uint32_t(x >> 32));
-}
-
-__global__ __launch_bounds__(kThr) void dfl_encode_kernel(const uint8_t *__restrict__ in, Geo g, DWs w,
-                                                          uint8_t *__restrict__ out) {
-    __shared__ uint32_t code[kSym];
-    __shared__ uint32_t wsum[kThr / 64];
-    const int c = blockIdx.x, a = c / g.cpa, k = c - a * g.cpa;
-    const int64_t beg = int64_t(k) * kChunk, len = min(kChunk, g.each - beg);
-    const int s = a * g.spa + int(beg / kSeg);
-    for (int i = threadIdx.x; i < kSym; i += kThr) code[i] = w.scode[int64_t(s) * kSym + i];
-    __syncthreads();
-    const uint8_t *src = in + int64_t(a) * g.each + beg;
-    const int t0 = threadIdx.x * kPerThr;
-    const int n = int(min<int64_t>(kPerThr, max<int64_t>(len - t0, 0)));
-    uint32_t wd[16];
-    load64(src, t0, n, wd);
-    auto byte = [&](int e) -> uint32_t { return (wd[e >> 2] >> (8 * (e & 3))) & 0xFFu; };
-    uint32_t bits = 0;
-#pragma unroll
-    for (int e = 0; e < kPerThr; ++e)
-        if (e < n) bits += code[byte(e)] >> 24;
-    // exclusive scan of the bit counts over the workgroup
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = bits;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int q = 0; q < wave; ++q) before += wsum[q];
-    const uint64_t seg_bit0 = w.soff[s] * 8;
-    const uint64_t pos = seg_bit0 + w.cbit[c] + before + incl - bits;
-    uint32_t *o = reinterpret_cast<uint32_t *>(out + a * g.bound);  // slots are 256-byte aligned
-    // The thread's codes, packed into 32-bit words: its first and last words
-    // may hold its neighbours' bits too (atomic OR into the zeroed slot), the
-    // words in between are its own (plain stores).
-    if (bits) {
-        const uint64_t w0 = pos >> 5, wl = (pos + bits - 1) >> 5;
-        uint64_t acc = 0;
-        int nacc = int(pos & 31);  // the first word's bits below the thread's start stay 0
-        uint64_t wi = w0;
-        auto emit = [&](uint32_t v) {
-            if (wi == w0 || wi == wl)
-                atomicOr(o + wi, v);
-            else
-                o[wi] = v;
-            ++wi;
-        };
-#pragma unroll
-        for (int e = 0; e < kPerThr; ++e) {
-            if (e < n) {
-                const uint32_t ce = code[byte(e)];
-                acc |= uint64_t(ce & 0xFFFFFFu) << nacc;
-                nacc += int(ce >> 24);
-                if (nacc >= 32) {
-                    emit(uint32_t(acc));
-                    acc >>= 32;
-                    nacc -= 32;
-                }
-            }
-        }
-        if (nacc > 0) emit(uint32_t(acc));
-    }
-    const int64_t sbeg = int64_t(beg / kSeg) * kSeg;
-    if (threadIdx.x == 0 && beg == sbeg) {
-        // the segment's first chunk: its block header
-        const uint32_t hb = w.shbits[s];
-        const uint32_t *h = w.shdr + int64_t(s) * kHdrWords;
-        for (uint32_t q = 0; q * 32 < hb; ++q) {
-            const int nb = int(min(32u, hb - q * 32));
-            or_bits(o, seg_bit0 + uint64_t(q) * 32, h[q], nb);
-        }
-    }
-    const int64_t slen = min(kSeg, g.each - sbeg);
-    if (threadIdx.x == kThr - 1 && beg + len == sbeg + slen) {
-        // the segment's last chunk: end of block, then the sync marker's FF FF
-        const uint32_t ce = code[256];
-        const uint64_t epos = seg_bit0 + w.cbit[c] + before + incl;
-        or_bits(o, epos, ce & 0xFFFFFFu, int(ce >> 24));
-        const uint64_t end = w.soff[s] + w.sbytes[s];  // byte after FF FF
-        or_bits(o, (end - 2) * 8, 0xFFFFu, 16);
-    }
-}
-
-// ================================================================ match mode
-// ofd_deflate_lz_batch: the same segments, chunks, spans and kernels, with
-// LZ77 matches at the element stride.  Every thread parses its own 64-byte
-// span greedily: at byte p it takes the longest run b[p+i] == b[p+i-D] over
-// the candidate distances D in {1, E, 2E} (E = the caller's element size; the
-// smaller D on ties) that stays inside the span, and codes it as a match when
-// it is kMinMatch bytes or more, else b[p] as a literal.  A match may read the
-// 2E <= 16 bytes before the span (they are input too), never bytes before its
-// own array.  The parse is a pure function of the span and those 16 bytes
-// (parse_span), so HIST and ENCODE both run it and no token is ever stored.
-constexpr int kLSym = 286;    // literals, end of block, 29 length symbols
-constexpr int kDSym = 30;     // distance symbols
-constexpr int kDOff = kLSym;  // the distance symbols follow in the joint tables ...
-constexpr int kAll = 320;     // ... of 316 entries, padded
-constexpr int kMinMatch = 3;
-constexpr int kCandDefault = 3;  // bit 0: distance 1, bit 1: distance 2E (E itself always)
-static_assert(kPerThr == 64, "a span's equality masks are 64-bit");
-// BFINAL BTYPE HLIT HDIST HCLEN, 19 code-length-code lengths, 316 lengths of <= 7 bits
-static_assert(14 + 19 * 3 + (kLSym + kDSym) * 7 <= kHdrWords * 32, "the block header must fit kHdrWords");
-
-int g_lz_cand = kCandDefault;
-
-size_t lz_ws_bytes(int64_t count, int64_t each) {
-    const int64_t cpa = (each + kChunk - 1) / kChunk, spa = (each + kSeg - 1) / kSeg;
-    const size_t nc = size_t(count * cpa), ns = size_t(count * spa);
-    return align256(nc * 2 * kAll) + 2 * align256(nc * 4) + align256(nc * 8) + 2 * align256(ns * 4 * kAll) +
-           align256(ns * 4 * kHdrWords) + 3 * align256(ns * 4) + align256(ns * 8);
-}
-
-DWs lz_carve(void *ws, int64_t count, const Geo &g) {
-    const size_t nc = size_t(count) * g.cpa, ns = size_t(count) * g.spa;
-    char *p = static_cast<char *>(ws);
-    DWs w;
-    w.chist = reinterpret_cast<uint16_t *>(p), p += align256(nc * 2 * kAll);  // [chunks][kAll]
-    w.ccrc = reinterpret_cast<uint32_t *>(p), p += align256(nc * 4);
-    w.cxb = reinterpret_cast<uint32_t *>(p), p += align256(nc * 4);
-    w.cbit = reinterpret_cast<uint64_t *>(p), p += align256(nc * 8);
-    w.shist = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kAll);  // [segs][kAll]  (zeroed per call)
-    w.scode = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kAll);  // [segs][kAll]
-    w.shdr = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4 * kHdrWords);
-    w.shbits = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
-    w.sbytes = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
-    w.scrc = reinterpret_cast<uint32_t *>(p), p += align256(ns * 4);
-    w.soff = reinterpret_cast<uint64_t *>(p);
-    return w;
-}
-
-// The 16 bytes before a span (zeros when there are none to read)
-__device__ __forceinline__ void load_hist16(const uint8_t *p, bool have, uint32_t hs[4]) {
-    hs[0] = hs[1] = hs[2] = hs[3] = 0u;
-    if (!have) return;
-    const uint8_t *h = p - 16;
-    if ((reinterpret_cast<uintptr_t>(h) & 15u) == 0) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(h);
-        hs[0] = v.x, hs[1] = v.y, hs[2] = v.z, hs[3] = v.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) hs[q] |= uint32_t(h[4 * q + r]) << (8 * r);
-    }
-}
-
-// ext = 16 history bytes then the span's 64, as 20 little-endian words.
-// Bit i of the result: span byte i equals the byte D before it.
-template <int D, int q>
-__device__ __forceinline__ uint64_t eq_nibble(const uint32_t ext[20]) {  // the mask's bits 4q .. 4q + 3
-    uint32_t prev;
-    if constexpr (D % 4 == 0)
-        prev = ext[4 + q - D / 4];
-    else
-        prev = uint32_t(((uint64_t(ext[4 + q]) << 32) | ext[3 + q]) >> (8 * (4 - D)));
-    const uint32_t x = ext[4 + q] ^ prev;
-    uint32_t t = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);  // 0x80 in every zero byte of x
-    t >>= 7;
-    return uint64_t((t | (t >> 7) | (t >> 14) | (t >> 21)) & 0xFu) << (4 * q);
-}
-
-template <int D, int... Q>
-__device__ __forceinline__ uint64_t eq_mask_seq(const uint32_t ext[20], std::integer_sequence<int, Q...>) {
-    return (eq_nibble<D, Q>(ext) | ...);
-}
-
-template <int D>
-__device__ __forceinline__ uint64_t eq_mask(const uint32_t ext[20]) {
-    static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16, "distance");
-    return eq_mask_seq<D>(ext, std::make_integer_sequence<int, 16>{});
-}
-
-// RFC 1951 3.2.5 for the distances in use (powers of two up to 16)
-__device__ __forceinline__ constexpr int dist_sym(int D) { return D == 1 ? 0 : D == 2 ? 1 : D == 4 ? 3 : D == 8 ? 5 : 7; }
-__device__ __forceinline__ constexpr int dist_xbits(int D) { return D == 8 ? 1 : D == 16 ? 2 : 0; }
-__device__ __forceinline__ constexpr uint32_t dist_xval(int D) { return D == 8 ? 1u : D == 16 ? 3u : 0u; }
-
-// length 3..257 -> symbol, extra bit count and value (258 is never emitted: a span has 64 bytes)
-__device__ __forceinline__ void len_sym(int len, int &sym, int &xb, uint32_t &xv) {
-    const int x = len - 3;
-    if (x < 8) {
-        sym = 257 + x, xb = 0, xv = 0u;
-    } else {
-        const int k = 29 - __clz(x);  // 8..15: 1 extra bit, 16..31: 2, 32..63: 3, ...
-        sym = 257 + 4 * (k + 1) + ((x >> k) & 3), xb = k, xv = uint32_t(x) & ((1u << k) - 1u);
-    }
-}
-
-// The greedy parse of one span: tok(e, is_match, length, D) for every token,
-// in order; e is the token's first byte as a std::integral_constant, so that
-// every index into the span's registers is a constant.  n = the span's bytes,
-// first = the span starts its array (no history to match).
-template <int E>
-struct SpanMasks {
-    uint64_t m1, me, m2;  // distance 1 (E > 1 only), E, 2E
-};
-
-template <int E>
-__device__ __forceinline__ SpanMasks<E> span_masks(const uint32_t ext[20], int n, bool first, int cand) {
-    const uint64_t live = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-    SpanMasks<E> m{0, 0, 0};
-    if (E > 1 && (cand & 1)) m.m1 = eq_mask<1>(ext) & live & (first ? ~0ull << 1 : ~0ull);
-    m.me = eq_mask<E>(ext) & live & (first ? ~0ull << E : ~0ull);
-    if (cand & 2) m.m2 = eq_mask<2 * E>(ext) & live & (first ? ~0ull << (2 * E) : ~0ull);
-    return m;
-}
-
-template <int e, int E, class F>
-__device__ __forceinline__ void parse_step(const SpanMasks<E> &m, int n, int &next, F &tok) {
-    if (e == next && e < n) {
-        auto run = [](uint64_t x) -> int {
-            const uint64_t y = ~(x >> e);
-            return y ? __builtin_ctzll(y) : 64;
-        };
-        int best = E > 1 ? run(m.m1) : 0, D = 1;
-        const int re = run(m.me), r2 = run(m.m2);
-        if (re > best) best = re, D = E;
-        if (r2 > best) best = r2, D = 2 * E;
-        const bool match = best >= kMinMatch;
-        tok(std::integral_constant<int, e>{}, match, best, D);
-        next = e + (match ? best : 1);
-    }
-}
-
-template <int E, class F, int... I>
-__device__ __forceinline__ void parse_steps(const SpanMasks<E> &m, int n, F &tok, std::integer_sequence<int, I...>) {
-    int next = 0;
-    (parse_step<I, E>(m, n, next, tok), ...);
-}
-
-template <int E, class F>
-__device__ __forceinline__ void parse_span(const SpanMasks<E> &m, int n, F &&tok) {
-    parse_steps<E>(m, n, tok, std::make_integer_sequence<int, kPerThr>{});
-}
-
-// byte e of the span in ext (e a constant)
-template <int e>
-__device__ __forceinline__ uint32_t span_byte(const uint32_t ext[20]) {
-    return (ext[4 + (e >> 2)] >> (8 * (e & 3))) & 0xFFu;
-}
-
-template <int E>
-__global__ __launch_bounds__(kThr) void dfl_lz_hist_kernel(const uint8_t *__restrict__ in, Geo g, DWs w, int cand) {
-    __shared__ uint32_t T[256];
-    __shared__ uint32_t H[kAll];
-    __shared__ uint32_t C[kThr];
-    __shared__ uint32_t X;
-    const int c = blockIdx.x, a = c / g.cpa, k = c - a * g.cpa;
-    const int64_t beg = int64_t(k) * kChunk, len = min(kChunk, g.each - beg);
-    const uint8_t *src = in + int64_t(a) * g.each + beg;
-    make_crc_table(T);
-    for (int i = threadIdx.x; i < kAll; i += kThr) H[i] = 0u;
-    if (threadIdx.x == 0) X = 0u;
-    __syncthreads();
-    const int t0 = threadIdx.x * kPerThr;
-    const int n = int(min<int64_t>(kPerThr, max<int64_t>(len - t0, 0)));
-    uint32_t ext[20];
-    load_hist16(src + t0, n > 0 && beg + t0 > 0, ext);
-    load64(src, t0, n, ext + 4);
-    uint32_t crc = 0xFFFFFFFFu;
-#pragma unroll
-    for (int e = 0; e < kPerThr; ++e)
-        if (e < n) crc = T[(crc ^ (ext[4 + (e >> 2)] >> (8 * (e & 3)))) & 0xFFu] ^ (crc >> 8);
-    crc = ~crc;
-    uint32_t zeros = 0, xbits = 0;
-    const SpanMasks<E> sm = span_masks<E>(ext, n, beg + t0 == 0, cand);
-    parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) {
-        if (!match) {
-            const uint32_t b = span_byte<decltype(e)::value>(ext);
-            if (b == 0u)
-                ++zeros;
-            else
-                atomicAdd(&H[b], 1u);
-        } else {
-            int sym, xb;
-            uint32_t xv;
-            len_sym(mlen, sym, xb, xv);
-            atomicAdd(&H[sym], 1u);
-            atomicAdd(&H[kDOff + dist_sym(D)], 1u);
-            xbits += uint32_t(xb + dist_xbits(D));
-        }
-    });
-    // zero literals dominate what is left: one wave sum, as in the literal HIST
-    for (int d = 32; d > 0; d >>= 1) {
-        zeros += __shfl_xor(zeros, d);
-        xbits += __shfl_xor(xbits, d);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (zeros) atomicAdd(&H[0], zeros);
-        if (xbits) atomicAdd(&X, xbits);
-    }
-    C[threadIdx.x] = crc;
-    __syncthreads();
-    for (int s = 1; s < kThr; s <<= 1) {
-        if ((threadIdx.x & (2 * s - 1)) == 0 && threadIdx.x + s < kThr) {
-            const int64_t lb = min<int64_t>(int64_t(s) * kPerThr, max<int64_t>(len - int64_t(threadIdx.x + s) * kPerThr, 0));
-            if (lb > 0) C[threadIdx.x] = crc_combine(C[threadIdx.x], C[threadIdx.x + s], uint64_t(lb));
-        }
-        __syncthreads();
-    }
-    const int seg = a * g.spa + int(beg / kSeg);
-    for (int i = threadIdx.x; i < kAll; i += kThr) {
-        const uint32_t h = H[i];
-        w.chist[int64_t(c) * kAll + i] = uint16_t(h);
-        if (h) atomicAdd(&w.shist[int64_t(seg) * kAll + i], h);
-    }
-    if (threadIdx.x == 0) {
-        w.ccrc[c] = len > 0 ? C[0] : 0u;
-        w.cxb[c] = X;
-    }
-}
-
 // Two trees per segment: literal / length (<= 286 symbols) and distance (<= 30).
 // zlib's inflater accepts exactly these distance codes: no match in the
-// segment -> one distance length 0; one distance symbol -> that symbol with
-// length 1 (incomplete, allowed); two or more -> a complete (Huffman) code.
-__global__ __launch_bounds__(kThr) void dfl_lz_code_kernel(Geo g, DWs w) {
+// segment (always so in the literal mode) -> one distance length 0; one
+// distance symbol -> that symbol with length 1 (incomplete, allowed); two or
+// more -> a complete (Huffman) code.
+template <bool kMatch>
+__global__ __launch_bounds__(kThr) void dfl_code_kernel(Geo g, DWs w) {
+    constexpr int kHist = hist_width(kMatch), kCode = code_width(kMatch);
     __shared__ HuffLds L;
     __shared__ uint32_t f[512];
     __shared__ uint32_t code[kAll];  // [0, 286) literal / length, [286, 316) distance
@@ -782,23 +548,26 @@ __global__ __launch_bounds__(kThr) void dfl_lz_code_kernel(Geo g, DWs w) {
     const int s = blockIdx.x, a = s / g.spa, k = s - a * g.spa;
     const int64_t sbeg = int64_t(k) * kSeg, slen = min(kSeg, g.each - sbeg);
     const int c0 = a * g.cpa + int(sbeg / kChunk), nch = int((slen + kChunk - 1) / kChunk);
-    const uint32_t *sh = w.shist + int64_t(s) * kAll;
-    for (int i = threadIdx.x; i < 512; i += kThr) f[i] = i == 256 ? 1u : (i < kLSym ? sh[i] : 0u);
+    const uint32_t *sh = w.shist + int64_t(s) * kHist;
+    // the end of block occurs once; symbols past the mode's counts never
+    for (int i = threadIdx.x; i < 512; i += kThr) f[i] = i == 256 ? 1u : (i < kLSym && i < kHist ? sh[i] : 0u);
     for (int i = threadIdx.x; i < kHdrWords; i += kThr) hdr[i] = 0u;
     for (int i = threadIdx.x; i < kAll; i += kThr) code[i] = 0u;
     if (threadIdx.x == 0) {
         int hlit = 257, hdist = 1, nd = 0;
-        for (int i = 257; i < kLSym; ++i)
-            if (sh[i]) hlit = i + 1;
-        for (int i = 0; i < kDSym; ++i)
-            if (sh[kDOff + i]) hdist = i + 1, ++nd;
+        if constexpr (kMatch) {
+            for (int i = 257; i < kLSym; ++i)
+                if (sh[i]) hlit = i + 1;
+            for (int i = 0; i < kDSym; ++i)
+                if (sh[kDOff + i]) hdist = i + 1, ++nd;
+        }
         s_hlit = hlit, s_hdist = hdist, s_nd = nd;
     }
     __syncthreads();
     huff_lengths(f, kLSym, kMaxLen, L);
     if (threadIdx.x == 0) canonical(L.len, kLSym, code);
     __syncthreads();
-    if (s_nd > 0) {  // the same in every thread
+    if (kMatch && s_nd > 0) {  // the same in every thread
         for (int i = threadIdx.x; i < 512; i += kThr) f[i] = i < kDSym ? sh[kDOff + i] : 0u;
         __syncthreads();
         huff_lengths(f, kDSym, kMaxLen, L);
@@ -833,17 +602,18 @@ __global__ __launch_bounds__(kThr) void dfl_lz_code_kernel(Geo g, DWs w) {
     }
     __syncthreads();
     for (int i = threadIdx.x; i < kHdrWords; i += kThr) w.shdr[int64_t(s) * kHdrWords + i] = hdr[i];
-    for (int i = threadIdx.x; i < kAll; i += kThr) w.scode[int64_t(s) * kAll + i] = code[i];
+    for (int i = threadIdx.x; i < kCode; i += kThr) w.scode[int64_t(s) * kCode + i] = code[i];
     // chunk bit counts: its symbols' code lengths plus its matches' extra bits; one wave per chunk
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int q = wave; q < nch; q += kThr / 64) {
         uint32_t bits = 0;
-        for (int i = lane; i < kAll; i += 64) bits += uint32_t(w.chist[int64_t(c0 + q) * kAll + i]) * (code[i] >> 24);
+        for (int i = lane; i < kHist; i += 64) bits += uint32_t(w.chist[int64_t(c0 + q) * kHist + i]) * (code[i] >> 24);
         for (int d = 32; d > 0; d >>= 1) bits += __shfl_xor(bits, d);
-        if (lane == 0) cb[q] = uint64_t(bits) + w.cxb[c0 + q];
+        if (lane == 0) cb[q] = uint64_t(bits) + (kMatch ? w.cxb[c0 + q] : 0u);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
+        // in order: each chunk's first code sits after the header and the chunks before it
         uint64_t acc = w.shbits[s];
         for (int q = 0; q < nch; ++q) {
             w.cbit[c0 + q] = acc;
@@ -853,6 +623,7 @@ __global__ __launch_bounds__(kThr) void dfl_lz_code_kernel(Geo g, DWs w) {
         acc += 3;                                  // sync flush: an empty stored block's header ...
         const uint64_t bytes = (acc + 7) / 8 + 4;  // ... padded to a byte, LEN 0000, NLEN FFFF
         w.sbytes[s] = uint32_t(bytes);
+        // segment CRC from its chunks' CRCs
         uint32_t crc = w.ccrc[c0];
         for (int q = 1; q < nch; ++q) {
             const int64_t lq = min(kChunk, slen - int64_t(q) * kChunk);
@@ -862,35 +633,72 @@ __global__ __launch_bounds__(kThr) void dfl_lz_code_kernel(Geo g, DWs w) {
     }
 }
 
+// ---------------------------------------------------------------- SCAN
+__global__ void dfl_scan_kernel(Geo g, DWs w, uint8_t *__restrict__ out, uint64_t *__restrict__ sizes,
+                                uint32_t *__restrict__ crcs, int64_t count) {
+    const int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (a >= count) return;
+    uint64_t off = 0;
+    uint32_t crc = 0;
+    for (int k = 0; k < g.spa; ++k) {
+        const int64_t s = a * g.spa + k;
+        w.soff[s] = off;
+        off += w.sbytes[s];
+        const int64_t lk = min(kSeg, g.each - int64_t(k) * kSeg);
+        crc = k == 0 ? w.scrc[s] : crc_combine(crc, w.scrc[s], uint64_t(lk));
+    }
+    uint8_t *o = out + a * g.bound;
+    o[off] = 0x03;  // final empty fixed block: BFINAL 1, BTYPE 1, end of block
+    o[off + 1] = 0x00;
+    sizes[a] = off + 2;
+    crcs[a] = g.spa ? crc : 0u;
+}
+
+// ---------------------------------------------------------------- ENCODE
+__device__ __forceinline__ void or_bits(uint32_t *o, uint64_t pos, uint64_t v, int n) {  // n <= 32, into zeroed memory
+    const uint64_t wd = pos >> 5;
+    const int sh = int(pos & 31);
+    const uint64_t x = (v & ((n == 32) ? 0xFFFFFFFFull : ((1ull << n) - 1))) << sh;
+    if (uint32_t(x)) atomicOr(o + wd, uint32_t(x));
+    if (uint32_t(x >> 32)) atomicOr(o + wd + 1, uint32_t(x >> 32));
+}
+
 template <int E>
-__global__ __launch_bounds__(kThr) void dfl_lz_encode_kernel(const uint8_t *__restrict__ in, Geo g, DWs w,
-                                                             uint8_t *__restrict__ out, int cand) {
-    __shared__ uint32_t code[kAll];
+__global__ __launch_bounds__(kThr) void dfl_encode_kernel(const uint8_t *__restrict__ in, Geo g, DWs w,
+                                                          uint8_t *__restrict__ out, int cand) {
+    constexpr int kCode = code_width(E != 0);
+    __shared__ uint32_t code[kCode];
     __shared__ uint32_t wsum[kThr / 64];
     const int c = blockIdx.x, a = c / g.cpa, k = c - a * g.cpa;
     const int64_t beg = int64_t(k) * kChunk, len = min(kChunk, g.each - beg);
     const int s = a * g.spa + int(beg / kSeg);
-    for (int i = threadIdx.x; i < kAll; i += kThr) code[i] = w.scode[int64_t(s) * kAll + i];
+    for (int i = threadIdx.x; i < kCode; i += kThr) code[i] = w.scode[int64_t(s) * kCode + i];
     __syncthreads();
     const uint8_t *src = in + int64_t(a) * g.each + beg;
     const int t0 = threadIdx.x * kPerThr;
     const int n = int(min<int64_t>(kPerThr, max<int64_t>(len - t0, 0)));
-    const bool first = beg + t0 == 0;
     uint32_t ext[20];
-    load_hist16(src + t0, n > 0 && !first, ext);
-    load64(src, t0, n, ext + 4);
-    const SpanMasks<E> sm = span_masks<E>(ext, n, first, cand);
-    uint32_t bits = 0;
-    parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) {
+    load_span<E>(src, beg, t0, n, ext);
+    const SpanMasks<E> sm = span_masks<E>(ext, n, beg + t0 == 0, cand);
+    // A token's code pieces, in stream order, each <= 20 bits LSB first, to
+    // put(value, bit count): a literal's code; a match's length code with its
+    // extra bits, then its distance code with its extra bits.
+    auto pieces = [&](auto e, bool match, int mlen, int D, auto &put) {
         if (!match) {
-            bits += code[span_byte<decltype(e)::value>(ext)] >> 24;
+            const uint32_t ce = code[span_byte<decltype(e)::value>(ext)];
+            put(ce & 0xFFFFFFu, int(ce >> 24));
         } else {
             int sym, xb;
             uint32_t xv;
             len_sym(mlen, sym, xb, xv);
-            bits += (code[sym] >> 24) + uint32_t(xb) + (code[kDOff + dist_sym(D)] >> 24) + uint32_t(dist_xbits(D));
+            const uint32_t cl = code[sym], cd = code[kDOff + dist_sym(D)];
+            put((cl & 0xFFFFFFu) | (xv << (cl >> 24)), int(cl >> 24) + xb);
+            put((cd & 0xFFFFFFu) | (dist_xval(D) << (cd >> 24)), int(cd >> 24) + dist_xbits(D));
         }
-    });
+    };
+    uint32_t bits = 0;
+    auto count = [&](uint32_t, int nb) { bits += uint32_t(nb); };
+    parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) { pieces(e, match, mlen, D, count); });
     // exclusive scan of the bit counts over the workgroup
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t incl = bits;
@@ -905,48 +713,36 @@ __global__ __launch_bounds__(kThr) void dfl_lz_encode_kernel(const uint8_t *__re
     const uint64_t seg_bit0 = w.soff[s] * 8;
     const uint64_t pos = seg_bit0 + w.cbit[c] + before + incl - bits;
     uint32_t *o = reinterpret_cast<uint32_t *>(out + a * g.bound);  // slots are 256-byte aligned
-    // first and last word by atomic OR into the zeroed slot, the words between by plain stores
+    // The thread's codes, packed into 32-bit words: its first and last words
+    // may hold its neighbours' bits too (atomic OR into the zeroed slot), the
+    // words in between are its own (plain stores).
     if (bits) {
         const uint64_t w0 = pos >> 5, wl = (pos + bits - 1) >> 5;
         uint64_t acc = 0;
-        int nacc = int(pos & 31);
+        int nacc = int(pos & 31);  // the first word's bits below the thread's start stay 0
         uint64_t wi = w0;
-        auto add = [&](uint32_t v, int nb) {  // nb <= 20 bits, LSB first
+        auto emit = [&](uint32_t v) {
+            if (wi == w0 || wi == wl)
+                atomicOr(o + wi, v);
+            else
+                o[wi] = v;
+            ++wi;
+        };
+        auto add = [&](uint32_t v, int nb) {
             acc |= uint64_t(v) << nacc;
             nacc += nb;
             if (nacc >= 32) {
-                if (wi == w0 || wi == wl)
-                    atomicOr(o + wi, uint32_t(acc));
-                else
-                    o[wi] = uint32_t(acc);
-                ++wi;
+                emit(uint32_t(acc));
                 acc >>= 32;
                 nacc -= 32;
             }
         };
-        parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) {
-            if (!match) {
-                const uint32_t ce = code[span_byte<decltype(e)::value>(ext)];
-                add(ce & 0xFFFFFFu, int(ce >> 24));
-            } else {
-                // length code, its extra bits, distance code, its extra bits
-                int sym, xb;
-                uint32_t xv;
-                len_sym(mlen, sym, xb, xv);
-                const uint32_t cl = code[sym], cd = code[kDOff + dist_sym(D)];
-                add((cl & 0xFFFFFFu) | (xv << (cl >> 24)), int(cl >> 24) + xb);
-                add((cd & 0xFFFFFFu) | (dist_xval(D) << (cd >> 24)), int(cd >> 24) + dist_xbits(D));
-            }
-        });
-        if (nacc > 0) {
-            if (wi == w0 || wi == wl)
-                atomicOr(o + wi, uint32_t(acc));
-            else
-                o[wi] = uint32_t(acc);
-        }
+        parse_span<E>(sm, n, [&](auto e, bool match, int mlen, int D) { pieces(e, match, mlen, D, add); });
+        if (nacc > 0) emit(uint32_t(acc));
     }
     const int64_t sbeg = int64_t(beg / kSeg) * kSeg;
     if (threadIdx.x == 0 && beg == sbeg) {
+        // the segment's first chunk: its block header
         const uint32_t hb = w.shbits[s];
         const uint32_t *h = w.shdr + int64_t(s) * kHdrWords;
         for (uint32_t q = 0; q * 32 < hb; ++q) {
@@ -956,6 +752,7 @@ __global__ __launch_bounds__(kThr) void dfl_lz_encode_kernel(const uint8_t *__re
     }
     const int64_t slen = min(kSeg, g.each - sbeg);
     if (threadIdx.x == kThr - 1 && beg + len == sbeg + slen) {
+        // the segment's last chunk: end of block, then the sync marker's FF FF
         const uint32_t ce = code[256];
         const uint64_t epos = seg_bit0 + w.cbit[c] + before + incl;
         or_bits(o, epos, ce & 0xFFFFFFu, int(ce >> 24));
@@ -964,15 +761,56 @@ __global__ __launch_bounds__(kThr) void dfl_lz_encode_kernel(const uint8_t *__re
     }
 }
 
+// ---------------------------------------------------------------- host
+// The kernels of one call in mode E (0: literal); an empty array is its final block alone
+using Launch = void (*)(const uint8_t *, uint8_t *, const Geo &, const DWs &, int64_t, uint64_t *, uint32_t *, int,
+                        hipStream_t);
+
 template <int E>
-void lz_launch(const uint8_t *src, uint8_t *dst, const Geo &g, const DWs &w, int64_t count, uint64_t *sizes,
-               uint32_t *crcs, int cand, hipStream_t st) {
+void launch(const uint8_t *src, uint8_t *dst, const Geo &g, const DWs &w, int64_t count, uint64_t *sizes, uint32_t *crcs,
+            int cand, hipStream_t st) {
     const unsigned nc = unsigned(count * g.cpa), ns = unsigned(count * g.spa);
-    hipLaunchKernelGGL(dfl_lz_hist_kernel<E>, dim3(nc), dim3(kThr), 0, st, src, g, w, cand);
-    hipLaunchKernelGGL(dfl_lz_code_kernel, dim3(ns), dim3(kThr), 0, st, g, w);
+    if (nc) {
+        hipLaunchKernelGGL(dfl_hist_kernel<E>, dim3(nc), dim3(kThr), 0, st, src, g, w, cand);
+        hipLaunchKernelGGL(dfl_code_kernel<E != 0>, dim3(ns), dim3(kThr), 0, st, g, w);
+    }
     hipLaunchKernelGGL(dfl_scan_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, st, g, w, dst, sizes, crcs,
                        count);
-    hipLaunchKernelGGL(dfl_lz_encode_kernel<E>, dim3(nc), dim3(kThr), 0, st, src, g, w, dst, cand);
+    if (nc) hipLaunchKernelGGL(dfl_encode_kernel<E>, dim3(nc), dim3(kThr), 0, st, src, g, w, dst, cand);
+}
+
+// Both entry points.  They report a bad workspace at different places: the
+// match mode before anything is enqueued, the literal mode after the slots'
+// memset (and so after that memset's own error).
+int deflate_batch(Launch launch, bool match, const void *in, int64_t count, int64_t bytes_each, void *out,
+                  uint64_t *sizes, uint32_t *crcs, void *workspace, size_t workspace_bytes, void *stream) {
+    if (count < 0 || bytes_each < 0) return OFD_FW_EINVAL;
+    if (count == 0) return OFD_FW_OK;
+    if (!out || !sizes || !crcs || (bytes_each > 0 && !in)) return OFD_FW_EINVAL;
+    if (reinterpret_cast<uintptr_t>(out) & 255u) return OFD_FW_EALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Geo g;
+    g.each = bytes_each;
+    g.cpa = int((bytes_each + kChunk - 1) / kChunk);
+    g.spa = int((bytes_each + kSeg - 1) / kSeg);
+    g.bound = int64_t(ofd_deflate_bound(bytes_each));
+    if (int64_t(count) * g.cpa >= (int64_t(1) << 31)) return OFD_FW_ETOOBIG;
+    const bool ws_bad = bytes_each > 0 && (!workspace || workspace_bytes < ws_bytes(count, bytes_each, match) ||
+                                           (reinterpret_cast<uintptr_t>(workspace) & 255u));
+    if (match && ws_bad) return OFD_FW_EWORKSPACE;
+    hipError_t e = hipMemsetAsync(out, 0, size_t(count) * size_t(g.bound), st);
+    if (e != hipSuccess) return int(e);
+    if (ws_bad) return OFD_FW_EWORKSPACE;
+    DWs w{};
+    if (bytes_each > 0) {
+        const size_t ns = size_t(count) * g.spa;
+        ws_layout(workspace, size_t(count) * g.cpa, ns, match, &w);
+        e = hipMemsetAsync(w.shist, 0, ns * 4 * hist_width(match), st);
+        if (e != hipSuccess) return int(e);
+    }
+    launch(static_cast<const uint8_t *>(in), static_cast<uint8_t *>(out), g, w, count, sizes, crcs, g_lz_cand, st);
+    e = hipGetLastError();
+    return e == hipSuccess ? OFD_FW_OK : int(e);
 }
 
 }  // namespace
@@ -988,45 +826,12 @@ size_t ofd_deflate_bound(int64_t bytes_each) {
 
 size_t ofd_deflate_workspace_bytes(int64_t count, int64_t bytes_each) {
     if (count <= 0 || bytes_each <= 0) return 0;
-    return ws_bytes(count, bytes_each);
+    return ws_bytes(count, bytes_each, false);
 }
 
 int ofd_deflate_batch(const void *in, int64_t count, int64_t bytes_each, void *out, uint64_t *sizes, uint32_t *crcs,
                       void *workspace, size_t workspace_bytes, void *stream) {
-    if (count < 0 || bytes_each < 0) return OFD_FW_EINVAL;
-    if (count == 0) return OFD_FW_OK;
-    if (!out || !sizes || !crcs || (bytes_each > 0 && !in)) return OFD_FW_EINVAL;
-    if (reinterpret_cast<uintptr_t>(out) & 255u) return OFD_FW_EALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Geo g;
-    g.each = bytes_each;
-    g.cpa = int((bytes_each + kChunk - 1) / kChunk);
-    g.spa = int((bytes_each + kSeg - 1) / kSeg);
-    g.bound = int64_t(ofd_deflate_bound(bytes_each));
-    if (int64_t(count) * g.cpa >= (int64_t(1) << 31)) return OFD_FW_ETOOBIG;
-    hipError_t e = hipMemsetAsync(out, 0, size_t(count) * size_t(g.bound), st);
-    if (e != hipSuccess) return int(e);
-    if (bytes_each == 0) {  // an empty array: the final block alone
-        hipLaunchKernelGGL(dfl_scan_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, st, g, DWs{},
-                           static_cast<uint8_t *>(out), sizes, crcs, count);
-        e = hipGetLastError();
-        return e == hipSuccess ? OFD_FW_OK : int(e);
-    }
-    if (!workspace || workspace_bytes < ws_bytes(count, bytes_each) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return OFD_FW_EWORKSPACE;
-    const DWs w = carve(workspace, count, g);
-    e = hipMemsetAsync(w.shist, 0, size_t(count) * g.spa * 1024, st);
-    if (e != hipSuccess) return int(e);
-    const unsigned nc = unsigned(count * g.cpa), ns = unsigned(count * g.spa);
-    const uint8_t *src = static_cast<const uint8_t *>(in);
-    uint8_t *dst = static_cast<uint8_t *>(out);
-    hipLaunchKernelGGL(dfl_hist_kernel, dim3(nc), dim3(kThr), 0, st, src, g, w);
-    hipLaunchKernelGGL(dfl_code_kernel, dim3(ns), dim3(kThr), 0, st, g, w);
-    hipLaunchKernelGGL(dfl_scan_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, st, g, w, dst, sizes, crcs,
-                       count);
-    hipLaunchKernelGGL(dfl_encode_kernel, dim3(nc), dim3(kThr), 0, st, src, g, w, dst);
-    e = hipGetLastError();
-    return e == hipSuccess ? OFD_FW_OK : int(e);
+    return deflate_batch(launch<0>, false, in, count, bytes_each, out, sizes, crcs, workspace, workspace_bytes, stream);
 }
 
 size_t ofd_deflate_lz_bound(int64_t bytes_each) {
@@ -1041,7 +846,7 @@ size_t ofd_deflate_lz_bound(int64_t bytes_each) {
 
 size_t ofd_deflate_lz_workspace_bytes(int64_t count, int64_t bytes_each) {
     if (count <= 0 || bytes_each <= 0) return 0;
-    return lz_ws_bytes(count, bytes_each);
+    return ws_bytes(count, bytes_each, true);
 }
 
 int ofd_deflate_lz_set_candidates(int mask) {
@@ -1052,43 +857,15 @@ int ofd_deflate_lz_set_candidates(int mask) {
 
 int ofd_deflate_lz_batch(const void *in, int64_t count, int64_t bytes_each, int elem_bytes, void *out, uint64_t *sizes,
                          uint32_t *crcs, void *workspace, size_t workspace_bytes, void *stream) {
-    if (count < 0 || bytes_each < 0) return OFD_FW_EINVAL;
-    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return OFD_FW_EINVAL;
-    if (count == 0) return OFD_FW_OK;
-    if (!out || !sizes || !crcs || (bytes_each > 0 && !in)) return OFD_FW_EINVAL;
-    if (reinterpret_cast<uintptr_t>(out) & 255u) return OFD_FW_EALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Geo g;
-    g.each = bytes_each;
-    g.cpa = int((bytes_each + kChunk - 1) / kChunk);
-    g.spa = int((bytes_each + kSeg - 1) / kSeg);
-    g.bound = int64_t(ofd_deflate_lz_bound(bytes_each));
-    if (int64_t(count) * g.cpa >= (int64_t(1) << 31)) return OFD_FW_ETOOBIG;
-    if (bytes_each > 0 &&
-        (!workspace || workspace_bytes < lz_ws_bytes(count, bytes_each) || (reinterpret_cast<uintptr_t>(workspace) & 255u)))
-        return OFD_FW_EWORKSPACE;
-    hipError_t e = hipMemsetAsync(out, 0, size_t(count) * size_t(g.bound), st);
-    if (e != hipSuccess) return int(e);
-    uint8_t *dst = static_cast<uint8_t *>(out);
-    if (bytes_each == 0) {  // an empty array: the final block alone
-        hipLaunchKernelGGL(dfl_scan_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, st, g, DWs{}, dst, sizes,
-                           crcs, count);
-        e = hipGetLastError();
-        return e == hipSuccess ? OFD_FW_OK : int(e);
-    }
-    const DWs w = lz_carve(workspace, count, g);
-    e = hipMemsetAsync(w.shist, 0, size_t(count) * g.spa * 4 * kAll, st);
-    if (e != hipSuccess) return int(e);
-    const uint8_t *src = static_cast<const uint8_t *>(in);
-    const int cand = g_lz_cand;
+    Launch l;
     switch (elem_bytes) {
-        case 1: lz_launch<1>(src, dst, g, w, count, sizes, crcs, cand, st); break;
-        case 2: lz_launch<2>(src, dst, g, w, count, sizes, crcs, cand, st); break;
-        case 4: lz_launch<4>(src, dst, g, w, count, sizes, crcs, cand, st); break;
-        default: lz_launch<8>(src, dst, g, w, count, sizes, crcs, cand, st); break;
+        case 1: l = launch<1>; break;
+        case 2: l = launch<2>; break;
+        case 4: l = launch<4>; break;
+        case 8: l = launch<8>; break;
+        default: return OFD_FW_EINVAL;
     }
-    e = hipGetLastError();
-    return e == hipSuccess ? OFD_FW_OK : int(e);
+    return deflate_batch(l, true, in, count, bytes_each, out, sizes, crcs, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
